@@ -3,7 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--op stage1|minify|validate_utf8]
                     [--workload large_random|amazon_ndjson|twitter_like|deep_nesting|escape_heavy] [--size BYTES]
-                    [--legs all|none|name,name]
+                    [--full [--legs all|none|name,name]] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path (sjgpu_*_device through the C-ABI) over one synthetic buffer that is already
 resident in HBM.  The TOP-LEVEL fields of the one JSON line are BASELINE.json configs[1]: stage 1 on 1 GiB of
@@ -16,6 +16,13 @@ BASELINE.json measured the same way (each with its own `roofline` and `cpu_basel
     config4_deep_nesting      1 GiB of brackets (one offset per byte)   config4_escape_heavy   backslash runs up to 64 KiB + 1
     plugin_host_path          sjgpu_stage1 with HOST buffers (PCIe both ways): 1 GiB document, 1 MB
                               parse_many-sized batches next to the reference's icelake kernel, sjgpu_stage1_many
+
+A plain run (no --full) measures the headline and nothing else: it builds what is stale, makes the buffer, warms up, times the K steps
+and prints the line (metric, value, unit, ms_per_step, ...).  --full adds what the rest of this docstring describes: the reference timed on the
+CPU (cpu_baseline) and the parity check of the timed output against it, the roofline (HIP-event kernel times inside the timed steps), the
+first-reps figure, the legs below, the N > 1 legs and the side-car file.  --dump-outputs DIR writes what the timed path returned in its last step
+(step_outputs: the result triple, the error code, the output buffer or a seeded sample of it) as DIR/<name>.npy; the inputs depend on the
+arguments alone, so two builds can be compared output for output.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): every rank scans its OWN 1 GiB shard (independent
 documents, SURVEY 8(e): no data-path collective), weak scaling; value = bytes all ranks scanned / max-over-ranks time;
@@ -99,18 +106,20 @@ def _leg_compact(name, leg):
     return out
 
 
-def compact_line(d):
-    """The ONE printed line from the full record: the contract's fields, numbers and short identifiers only, <= COMPACT_LINE_LIMIT characters."""
+def compact_line(d, full=True):
+    """The ONE printed line from the full record: the contract's fields, numbers and short identifiers only, <= COMPACT_LINE_LIMIT characters.
+    full=False (a plain run, which measures the headline alone): no roofline, reference, parity or side-car entries."""
     c = {k: d.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     cfg = d.get("config") or {}
     c["config"] = {"workload": _short(cfg.get("workload"), 160), "bytes_per_gpu": cfg.get("bytes_per_gpu"), "structurals": cfg.get("structurals"),
                    "library": cfg.get("library")}
-    c["roofline"] = _roofline_compact(d.get("roofline"))
-    c["cpu_baseline"] = _cpu_compact(d.get("cpu_baseline"))
-    if "cpu_baseline_threads" in d:
-        c["cpu_baseline_threads"] = _cpu_compact(d["cpu_baseline_threads"])
-    p = d.get("parity") or {}
-    c["parity"] = {k: p[k] for k in ("checked", "ok", "ranks_checked", "ranks_ok", "all_ranks_ok") if k in p}
+    if full:
+        c["roofline"] = _roofline_compact(d.get("roofline"))
+        c["cpu_baseline"] = _cpu_compact(d.get("cpu_baseline"))
+        if "cpu_baseline_threads" in d:
+            c["cpu_baseline_threads"] = _cpu_compact(d["cpu_baseline_threads"])
+        p = d.get("parity") or {}
+        c["parity"] = {k: p[k] for k in ("checked", "ok", "ranks_checked", "ranks_ok", "all_ranks_ok") if k in p}
     for k in ("first_reps_ms_per_step", "value_first_reps", "clock_warmup_calls", "n1_same_workload_GBps", "scaling_efficiency", "n_ranks_seen_by_rccl"):
         if k in d:
             c[k] = d[k]
@@ -131,7 +140,8 @@ def compact_line(d):
     ds = d.get("one_document_shards")
     if isinstance(ds, dict):
         c["one_document_shards"] = {"error": _short(ds["error"], 80)} if "error" in ds else {k: ds.get(k) for k in ("value_GBps", "total_structurals", "steps")}
-    c["detail"] = DETAIL_FILE
+    if full:
+        c["detail"] = DETAIL_FILE
     text = json.dumps(c, allow_nan=False, separators=(",", ":"))
     if len(text) > COMPACT_LINE_LIMIT:  # never let the line outgrow the capture again: drop what is least needed, say so
         for victim in ("one_document_shards", "legs"):
@@ -233,12 +243,14 @@ def make_workload(corpus, workload, size, seed):
 
 
 def device_leg(cx, op, workload, host, units, steps, warmup, pipeline, fence=None, cpu_iters=None, with_cpu=True, with_parity=None, parity_raises=True,
-               rank=0, world=1):
+               rank=0, world=1, full=True, keep_outputs=False):
     """One op over one resident buffer: K timed steps bracketed by synchronize (+ barrier), HIP-event kernel time from
     libsjgpu, exact parity of the timed buffer's output against the reference (count AND an order-sensitive digest).
     Three timed regions, in this order: (1) `steps` steps straight behind the --warmup steps -- what a cold 5 + 20 run gives, the way rounds 1-4a
     timed (first_reps_ms_per_step / value_first_reps); (2) N > 1 only: rank 0 ALONE over its own buffer while the other ranks wait in a barrier --
-    the same-workload single-rank figure the N-rank value is divided by (n1_same_workload); (3) behind clock_warmup: the sustained figure = `value`."""
+    the same-workload single-rank figure the N-rank value is divided by (n1_same_workload); (3) behind clock_warmup: the sustained figure = `value`.
+    full=False (a plain bench.py run) times region (3) alone, without the HIP-event profile (no roofline); keep_outputs=True returns what the last
+    timed step computed under "outputs" (step_outputs)."""
     torch, capi = cx.torch, cx.capi
     L = len(host)
     # every leg starts from an empty caching allocator: the split pipeline's pace depends on WHERE its buffers lie (profiles/r05_stream_ab.txt, session R: up to
@@ -271,14 +283,15 @@ def device_leg(cx, op, workload, host, units, steps, warmup, pipeline, fence=Non
     parser.result(stream)
     used = "-" if op == "validate_utf8" else parser.last_pipeline()
     kernel = parser.profile_kernel()
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        step()
-    sync()
-    dt_first = time.perf_counter() - t0
-    solo = None
-    if world > 1:  # every rank passes both fences; between them only rank 0 works
+    dt_first = solo = None
+    if full:
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            step()
+        sync()
+        dt_first = time.perf_counter() - t0
+    if full and world > 1:  # every rank passes both fences; between them only rank 0 works
         sync()
         if rank == 0:
             clock_warmup(torch, step)
@@ -293,15 +306,23 @@ def device_leg(cx, op, workload, host, units, steps, warmup, pipeline, fence=Non
                            "what an N = 1 run of THIS workload gives, measured inside this run"}
         sync()
     warm_calls = clock_warmup(torch, step)
-    parser.profile_enable(True)
+    parser.profile_enable(full)
     sync()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     sync()
     dt = time.perf_counter() - t0
+    if not full:
+        outputs = step_outputs(cx, op, parser, out, stream) if keep_outputs else None
+        parser.close()
+        del buf, out
+        return {"value": round(L * steps / dt / 1e9, 2), "unit": "GB/s", "ms_per_step": round(dt / steps * 1e3, 4), "bytes": L, "units": units,
+                "pipeline": used, "structurals": n if op == "stage1" else None, "out_bytes": out_len if op == "minify" else None,
+                "clock_warmup_calls": warm_calls, "outputs": outputs}
     ms_sum, calls = parser.profile_read()
     parser.profile_enable(False)
+    outputs = step_outputs(cx, op, parser, out, stream) if keep_outputs else None
     # slot 0 = clears + (first) scan kernel; slots 1, 2 hold the resolve and emit kernels of the split pipeline.
     # A single-pass call leaves them empty, and an empty event pair still measures ~5 us of event bookkeeping: not counted.
     single_kernel = "+" not in kernel
@@ -322,6 +343,8 @@ def device_leg(cx, op, workload, host, units, steps, warmup, pipeline, fence=Non
                      "timing": "hipEvent pairs around what one call enqueues on the launch stream (slot 0: clears and the scan kernel; slots 1-2: resolve and emit "
                                "kernels of the split pipeline, empty and not counted for a single-pass call), mean over the timed steps"},
     }
+    if outputs is not None:
+        leg["outputs"] = outputs
     if with_cpu:
         cb = cx.cpu().time_cpu(host, op, cpu_iters or cx.args.cpu_iters)
         leg["cpu_baseline"] = {"value": round(cb["value"], 3), "unit": "GB/s", "cores": cb["cores"], "kind": cb["kind"],
@@ -336,6 +359,58 @@ def device_leg(cx, op, workload, host, units, steps, warmup, pipeline, fence=Non
     parser.close()
     del buf, out
     return leg
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 21         # entries of a large output kept, at positions drawn with DUMP_SEED
+DUMP_EDGE = 1 << 16           # entries kept whole at each end of a large output
+DUMP_SEED = 20260101
+
+
+def _digest_limbs(d):
+    """a 64-bit digest as four 16-bit limbs, each exact in float64"""
+    return np.array([(d >> (16 * i)) & 0xFFFF for i in range(4)], dtype=np.float64)
+
+
+def step_outputs(cx, op, parser, out, stream):
+    """What a caller of the timed path receives from its last step, as float64 / float32 arrays for --dump-outputs: the result triple
+    (count, flags, output length) with its error code and, for stage1 / minify, the output buffer -- whole when it is small, otherwise its
+    first and last DUMP_EDGE entries, DUMP_SAMPLE entries at seeded positions (and the positions) and an order-sensitive digest of all of it."""
+    torch, capi = cx.torch, cx.capi
+    n, flags, out_len = parser.result(stream)
+    err = capi.stage1_error_from_flags(n, flags) if op == "stage1" else ((15 if flags & 1 else 0) if op == "minify" else (11 if flags & capi.F_UTF8_ERROR else 0))
+    res = {"result_count": np.array([n], dtype=np.float64), "result_flags": np.array([flags], dtype=np.float64),
+           "error_code": np.array([err], dtype=np.float64)}
+    if op == "validate_utf8":
+        res["utf8_valid"] = np.array([0 if flags & capi.F_UTF8_ERROR else 1], dtype=np.float64)
+        return res
+    if op == "stage1":
+        name, count, dtype = "structural_indexes", n + 3, np.float64  # the count plus the reference's three closing entries
+        res["structural_indexes_digest"] = _digest_limbs(position_digest_device(torch, out, count))
+        words = out[:count].to(torch.int64) & 0xFFFFFFFF
+    else:
+        name, count, dtype = "minified", out_len, np.float32
+        res["out_bytes"] = np.array([out_len], dtype=np.float64)
+        res["minified_digest"] = _digest_limbs(byte_digest_device(torch, out, count))
+        words = out[:count].to(torch.int64)
+    if count <= DUMP_SAMPLE + 2 * DUMP_EDGE:
+        res[name] = words.cpu().numpy().astype(dtype)
+    else:
+        res[name + "_head"] = words[:DUMP_EDGE].cpu().numpy().astype(dtype)
+        res[name + "_tail"] = words[count - DUMP_EDGE:].cpu().numpy().astype(dtype)
+        at = np.unique(np.random.default_rng(DUMP_SEED).integers(0, count, size=DUMP_SAMPLE, dtype=np.int64))
+        res[name + "_sample"] = words[torch.from_numpy(at).to(words.device)].cpu().numpy().astype(dtype)
+        res[name + "_sample_at"] = at.astype(np.float64)
+    return res
+
+
+def dump_outputs(where, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    os.makedirs(where, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(where, name + ".npy"), a)
 
 
 def parity_check(cx, op, host, parser, n, out_len, flags, out):
@@ -863,13 +938,17 @@ def main():
     ap.add_argument("--workload", default=None, choices=["large_random", "amazon_ndjson", "twitter_like", "deep_nesting", "escape_heavy"])
     ap.add_argument("--size", type=int, default=1 << 30, help="bytes per GPU")
     ap.add_argument("--pipeline", default=os.environ.get("SJGPU_PIPELINE", "auto"), choices=["auto", "fused", "split"])
-    ap.add_argument("--legs", default="all", help="N = 1: which of the other BASELINE configs to measure into the same line: all | none | comma list of "
+    ap.add_argument("--legs", default="all", help="--full, N = 1: which of the other BASELINE configs to measure into the same line: all | none | comma list of "
                     + ",".join(ALL_LEGS))
-    ap.add_argument("--ndjson-leg", type=int, default=-1, help="N > 1: 0 switches the NDJSON / one-document legs off")
+    ap.add_argument("--ndjson-leg", type=int, default=-1, help="--full, N > 1: 0 switches the NDJSON / one-document legs off")
     ap.add_argument("--cpu-iters", type=int, default=12)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for dry runs)")
     ap.add_argument("--share-device", action="store_true", help="dry run: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the reference on the CPU and the parity check against it, the "
+                    "roofline (HIP-event kernel times), the first-reps figure, the other legs (--legs, --ndjson-leg) and the side-car " + DETAIL_FILE)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step to DIR/<name>.npy "
+                    "(float64 / float32, at most 64 MB: a seeded sample of a large output)")
     args = ap.parse_args()
 
     import torch
@@ -883,8 +962,9 @@ def main():
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
-                                  "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]])
+        import subprocess
+        raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr",
+                                          "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]))
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -926,12 +1006,13 @@ def main():
     L = len(host)
     # the reference beside it: rank 0 times it (one thread on its own buffer; NDJSON adds all hardware threads);
     # EVERY rank checks its own output against the reference, the verdicts are reduced into the line
-    with_cpu = rank == 0 and not args.no_cpu_baseline
-    with_parity = not args.no_cpu_baseline
+    with_cpu = args.full and rank == 0 and not args.no_cpu_baseline
+    with_parity = args.full and not args.no_cpu_baseline
     leg = device_leg(cx, args.op, args.workload, host, units, args.steps, args.warmup, args.pipeline, fence=fence, with_cpu=with_cpu, with_parity=with_parity,
-                     parity_raises=world == 1, rank=rank, world=world)
+                     parity_raises=world == 1, rank=rank, world=world, full=args.full, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    outputs = leg.pop("outputs", None)
     parity_failed_somewhere = False
-    if world > 1:
+    if world > 1 and args.full:
         mine_ok = 1.0 if leg.get("parity", {}).get("ok", False) else 0.0
         pv = torch.tensor([mine_ok, 1.0 if "parity" in leg else 0.0], dtype=torch.float64, device="cuda")
         dist.all_reduce(pv)
@@ -949,7 +1030,7 @@ def main():
                                            "sample": f"rank 0's NDJSON buffer cut at newlines into {cb['cores']} slices, {cb['impl']} kernel, one parser per thread, "
                                                      f"{threads} hardware threads on the box", "structurals": cb["n"]}
     dt = leg["ms_per_step"] * 1e-3 * args.steps
-    dt_first = leg["first_reps_ms_per_step"] * 1e-3 * args.steps
+    dt_first = leg["first_reps_ms_per_step"] * 1e-3 * args.steps if args.full else dt
     if world > 1:
         t = torch.tensor([dt, dt_first], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -971,7 +1052,7 @@ def main():
                                    f"{leg['pipeline']} pipeline", "bytes_per_gpu": L, "units_per_gpu": units, "structurals": leg["structurals"],
                        "out_bytes": leg["out_bytes"], "parallelism": f"{world} independent shard(s), one rank per GPU, no data-path collective",
                        "library": os.path.basename(capi._paths.LIB_SJGPU)},
-            "roofline": leg["roofline"],
+            "roofline": leg.get("roofline"),
             "clock_warmup_calls": leg.get("clock_warmup_calls"),  # untimed calls in front of the timed region, on top of --warmup: see clock_warmup()
             # the same K steps timed straight behind the --warmup steps, before clock_warmup (MAX over ranks): what a cold `--warmup W --steps K` run gives
             "first_reps_ms_per_step": round(dt_first / args.steps * 1e3, 4), "value_first_reps": round(total_bytes * args.steps / dt_first / 1e9, 2),
@@ -981,6 +1062,11 @@ def main():
                                         "value(N) / (N x value(1)) compares like with like; configs[3] (sharded NDJSON + RCCL index concatenation) is "
                                         + ("`legs.config3_amazon_ndjson`" if world == 1 else "`config3_ndjson_sharded`") + " of this line",
         }
+        if not args.full:  # a plain run times the K steps behind clock_warmup and nothing else
+            for k in ("roofline", "first_reps_ms_per_step", "value_first_reps"):
+                del line[k]
+            line["timing"] = ("value / ms_per_step: K steps behind W warm-up steps + clock_warmup (40 ms of the same calls, untimed); --full adds the roofline, "
+                              "the first-reps figure, the reference and the other legs")
         if world > 1 and leg.get("n1_same_workload"):
             n1 = leg["n1_same_workload"]
             line["n1_same_workload_GBps"] = n1["value"]
@@ -992,7 +1078,7 @@ def main():
                 line[k] = leg[k]
 
     # ---- N = 1: the other BASELINE configs, same method, into the same line ----
-    if world == 1 and args.op == "stage1" and args.workload == "large_random" and args.legs != "none":
+    if args.full and world == 1 and args.op == "stage1" and args.workload == "large_random" and args.legs != "none":
         wanted = ALL_LEGS if args.legs == "all" else [x for x in args.legs.split(",") if x]
         legs = {}
         sub_steps, sub_warm = max(5, args.steps // 2), 2
@@ -1040,7 +1126,7 @@ def main():
 
     # ---- N > 1: BASELINE.json configs[3] (parse_many-style NDJSON shards, RCCL concatenation) and the one-document path ----
     ndjson = docshards = None
-    if world > 1 and args.op == "stage1" and args.ndjson_leg != 0:
+    if args.full and world > 1 and args.op == "stage1" and args.ndjson_leg != 0:
         try:
             ndjson = ndjson_leg(args, torch, dist, corpus, capi, rank, world, local_rank, fence)
         except Exception as e:  # the primary line must survive a failure here
@@ -1057,9 +1143,12 @@ def main():
             line["index_concat"] = ndjson.get("index_concat")
         if docshards is not None:
             line["one_document_shards"] = docshards
-        write_detail(line)
+        if args.full:
+            write_detail(line)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         sys.stdout.flush()
-        print(compact_line(line), flush=True)  # the ONE line, and the last one: <= 4 KB, numbers and identifiers (the full record: bench_detail.json)
+        print(compact_line(line, full=args.full), flush=True)  # the ONE line, and the last one: <= 4 KB, numbers and identifiers (the full record: bench_detail.json)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -10,13 +10,13 @@ O=gpurun_out
 T=${1:-r06}
 timeout 600 python __graft_entry__.py --smoke > $O/${T}_smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/${T}_smoke.log
 timeout 2400 python -m pytest tests -m gpu -q -x --timeout 1400 -p no:cacheprovider > $O/${T}_pytest_gpu.log 2>&1; echo "pytest rc=$?"; grep -n "passed\|failed" $O/${T}_pytest_gpu.log | tail -2
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err; echo "bench rc=$?"; tail -n 1 $O/${T}_bench_default.json | wc -c
+timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_bench_default.json 2> $O/${T}_bench_default.err; echo "bench rc=$?"; tail -n 1 $O/${T}_bench_default.json | wc -c
 cp bench_detail.json $O/${T}_bench_detail.json
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace -d $GRAFT_REPO_ROOT/gpurun_out/prof_${T}_bench_final -o b -- python $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $GRAFT_REPO_ROOT/gpurun_out/${T}_bench_profiled.json 2> $GRAFT_REPO_ROOT/gpurun_out/${T}_bench_profiled.err); echo "profiled bench rc=$?"
+R=$PWD; (cd /tmp && timeout 900 rocprofv3 --kernel-trace -d $R/$O/prof_${T}_bench_final -o b -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $R/$O/${T}_bench_profiled.json 2> $R/$O/${T}_bench_profiled.err); echo "profiled bench rc=$?"
 cp bench_detail.json $O/${T}_bench_profiled_detail.json
-timeout 600 python bench.py --workload amazon_ndjson > $O/${T}_bench_ndjson_n1.json 2> $O/${T}_bench_ndjson_n1.err; echo "ndjson n1 rc=$?"
+timeout 600 python bench.py --workload amazon_ndjson --full > $O/${T}_bench_ndjson_n1.json 2> $O/${T}_bench_ndjson_n1.err; echo "ndjson n1 rc=$?"
 cp bench_detail.json $O/${T}_bench_ndjson_n1_detail.json
-timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --backend gloo --share-device --size 268435456 > $O/${T}_bench_n2_dry.json 2> $O/${T}_bench_n2_dry.err; echo "n2 dry rc=$?"; tail -n 1 $O/${T}_bench_n2_dry.json | wc -c
+timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --backend gloo --share-device --size 268435456 --full > $O/${T}_bench_n2_dry.json 2> $O/${T}_bench_n2_dry.err; echo "n2 dry rc=$?"; tail -n 1 $O/${T}_bench_n2_dry.json | wc -c
 cp bench_detail.json $O/${T}_bench_n2_dry_detail.json
 bash scripts/gpu_pmc.sh "--op stage1" ${T}_headline "fetch write sq1 sq2" > $O/${T}_pmc_headline.log 2>&1; echo "pmc headline rc=$?"
 bash scripts/gpu_pmc.sh "--op stage1 --workload amazon_ndjson" ${T}_ndjson "fetch write sq1 sq2" > $O/${T}_pmc_ndjson.log 2>&1; echo "pmc ndjson rc=$?"

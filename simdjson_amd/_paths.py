@@ -12,6 +12,6 @@ REFERENCE_DIR = os.environ.get("SIMDJSON_REFERENCE", "/root/reference")
 
 LIB_SJGPU = os.environ.get("SJGPU_LIB") or os.path.join(LIB_DIR, "libsjgpu.so")  # HIP kernels + C-ABI (the product)
 LIB_CORPUS = os.path.join(LIB_DIR, "libsjcorpus.so")      # synthetic corpora (host tooling)
-LIB_PLUGIN = os.path.join(LIB_DIR, "libsimdjson_mi355x.so")  # simdjson::implementation shim (needs reference headers to build)
+LIB_PLUGIN = os.path.join(ORACLE_OUT, "libsimdjson_mi355x.so")  # simdjson::implementation shim (built against the reference's headers: beside the other reference builds)
 LIB_ORACLE = os.path.join(ORACLE_OUT, "libsjoracle.so")   # test infrastructure
 LIB_REF = os.path.join(ORACLE_OUT, "libsjref.so")         # test infrastructure (real reference)

@@ -208,3 +208,68 @@ def test_the_token_stream_s_cost_and_gain_are_in_the_line():
         # bytes from the same window: the stream is accepted and not read -- the same tape in the same time; two timed regions of one run differ by up
         # to 9 % with the clocks they meet: session r06f 1.508 / 1.640 ms, r06e 1.577 / 1.586)
         assert w["stage2_ms_per_call"] < 1.15 * leg["gpu_ms_per_call"] and "word for word" in w["parity"], kind
+
+
+def _bench():
+    import sys
+    sys.path.insert(0, _paths.REPO_ROOT)
+    import bench
+    return bench
+
+
+def test_the_plain_line_carries_the_headline_alone():
+    """A plain run (no --full) measures the headline and nothing else: its line has the contract's headline fields and none of what --full adds."""
+    bench = _bench()
+    d, _ = _final_line()
+    plain = {k: v for k, v in d.items() if k not in ("roofline", "cpu_baseline", "parity", "legs", "legs_failed", "first_reps_ms_per_step", "value_first_reps")}
+    c = _strict(bench.compact_line(plain, full=False))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "data", "config"):
+        assert c[key] == (d[key] if key != "config" else c[key]), key
+    for key in ("roofline", "cpu_baseline", "parity", "detail", "legs", "first_reps_ms_per_step"):
+        assert key not in c, key
+    assert _strict(bench.compact_line(d)) == _strict(bench.compact_line(d, full=True))
+
+
+class _FakeParser:
+    def __init__(self, n, flags, out_len):
+        self.triple = (n, flags, out_len)
+
+    def result(self, stream):
+        return self.triple
+
+
+def test_dumped_outputs_are_float_seeded_and_bounded(tmp_path):
+    """--dump-outputs: what the last step returned, as float64 / float32 .npy files under 64 MB in all; a large output is kept as its two ends, a sample at
+    seeded positions (the same positions in every run) and a digest of the whole; a small one whole."""
+    import numpy as np
+    import torch
+    from simdjson_amd import capi
+    bench = _bench()
+
+    class Cx:
+        pass
+    cx = Cx()
+    cx.torch, cx.capi = torch, capi
+    rng = np.random.default_rng(7)
+    for count in (1000, bench.DUMP_SAMPLE + 2 * bench.DUMP_EDGE + 12345):
+        idx = np.sort(rng.integers(0, 1 << 30, size=count + 16)).astype(np.int32)
+        out = torch.from_numpy(idx)
+        got = [bench.step_outputs(cx, "stage1", _FakeParser(count - 3, 0, 0), out, 0) for _ in range(2)]
+        assert got[0].keys() == got[1].keys() and all(np.array_equal(got[0][k], got[1][k]) for k in got[0])
+        res = got[0]
+        assert res["result_count"][0] == count - 3 and res["error_code"][0] == 0
+        assert sum(a.nbytes for a in res.values()) <= bench.DUMP_LIMIT_BYTES
+        limbs = res["structural_indexes_digest"].astype(np.uint64)
+        assert int(sum(int(x) << (16 * i) for i, x in enumerate(limbs))) == bench.position_digest_host(idx[:count].astype(np.uint32))
+        if "structural_indexes" in res:
+            assert np.array_equal(res["structural_indexes"], idx[:count].astype(np.float64))
+        else:
+            at = res["structural_indexes_sample_at"].astype(np.int64)
+            assert len(at) > bench.DUMP_SAMPLE // 2 and at.max() < count and np.all(np.diff(at) > 0)
+            assert np.array_equal(res["structural_indexes_sample"], idx[at].astype(np.float64))
+            assert np.array_equal(res["structural_indexes_head"], idx[:bench.DUMP_EDGE].astype(np.float64))
+            assert np.array_equal(res["structural_indexes_tail"], idx[count - bench.DUMP_EDGE:count].astype(np.float64))
+        bench.dump_outputs(str(tmp_path / str(count)), res)
+        for name, a in res.items():
+            back = np.load(tmp_path / str(count) / (name + ".npy"))
+            assert back.dtype in (np.float32, np.float64) and np.array_equal(back, a)

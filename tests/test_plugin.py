@@ -1,8 +1,8 @@
 """The drop-in boundary: simdjson's own front-ends (dom::parser, ondemand::parser, parse_many, minify,
 validate_utf8) running on the UNMODIFIED reference library with the mi355x implementation activated
-(simdjson_amd/csrc/plugin/, tests/plugin/plugin_test.cpp).  The binaries are built in the build container
-(they need the reference's headers and library object) into build/tests/ and travel with the repo; a binary
-that was built from other sources than the ones in the tree is refused (build.binary_is_current)."""
+(simdjson_amd/csrc/plugin/, tests/plugin/plugin_test.cpp).  The binaries are built where the reference is
+(they need its headers and library object) into oracle/_ref/tests/, which is kept where the reference is absent; a
+binary that was built from other sources than the ones in the tree is refused (build.binary_is_current)."""
 import os
 import subprocess
 
@@ -20,7 +20,7 @@ def _binary():
     build.build_plugin()
     exe = build.build_plugin_test()
     if exe is not None:
-        assert build.binary_is_current("plugin_test"), "build/tests/plugin_test is stale (sources changed since it was built)"
+        assert build.binary_is_current("plugin_test"), "oracle/_ref/tests/plugin_test is stale (sources changed since it was built)"
     return exe
 
 
@@ -57,7 +57,7 @@ def test_reference_own_test_programs_on_mi355x(name):
     _binary()
     built = {os.path.basename(p): p for p in build.build_reference_tests()}
     assert name in built, f"{name} was not built (needs the build container)"
-    assert build.binary_is_current(name), f"build/tests/{name} is stale (sources changed since it was built)"
+    assert build.binary_is_current(name), f"oracle/_ref/tests/{name} is stale (sources changed since it was built)"
     out = subprocess.run([built[name]], capture_output=True, text=True, timeout=1200, cwd=_paths.REPO_ROOT)  # the data directory is compiled in relative to the checkout
     tail = (out.stdout[-2500:] + out.stderr[-1500:])
     assert out.returncode == 0, tail
@@ -72,7 +72,7 @@ def _intree(name):
     _binary()
     built = {os.path.basename(p): p for p in build.build_intree()}
     assert name in built, f"{name} was not built (needs the build container)"
-    assert build.binary_is_current(name), f"build/tests/{name} is stale (sources changed since it was built)"
+    assert build.binary_is_current(name), f"oracle/_ref/tests/{name} is stale (sources changed since it was built)"
     return built[name]
 
 
