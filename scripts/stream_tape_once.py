@@ -1,0 +1,125 @@
+"""One measurement of stage 2 over a document stream (sjgpu_stage2_many_device) beside the single document's call on the same records.
+
+Builds an amazon-like NDJSON stream of --mib MiB (simdjson_amd/csrc/corpus.c) and the SAME records wrapped as one array [r1,r2,...], runs stage 1 on
+both, and times in one process, warmed, alternating, with events on the stream, median of --reps:
+  (a) sjgpu_stage2_many_device on the stream     one tape per record
+  (b) sjgpu_stage2_device on the array           the single document's road over the same tokens
+  (c) the reference's stage 2 on the array, one core (oracle/_ref/libsjref.so, where it is present)
+  (d) (a) on the stream with its LAST record broken: two runs by design
+Prints one JSON line.  For the per-kernel split run it once more under `rocprofv3 --kernel-trace --stats` with --reps 3 (tracing slows the host: the
+timings of that run are not the ones to quote)."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from simdjson_amd import _paths, build, capi, corpus  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mib", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--no-cpu", action="store_true")
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: this script measures, it does not fall back")
+    build.build_sjgpu()
+    stream_host, lines = corpus.amazon_ndjson(args.mib << 20, 7)
+    if stream_host[-1] != 0x0A:
+        stream_host = np.concatenate([stream_host, np.frombuffer(b"\n", np.uint8)])
+    array_host = np.concatenate([np.frombuffer(b"[", np.uint8), stream_host])
+    nl = np.flatnonzero(array_host == 0x0A)  # (a JSON string holds no raw newline: every one of them ends a record)
+    assert len(nl) == lines, (len(nl), lines)
+    array_host[nl] = ord(",")
+    array_host[nl[-1]] = ord("]")
+    broken_host = stream_host.copy()
+    assert broken_host[-2] == ord("]")  # (a record is an array; the stream ends "]\n")
+    broken_host[-2] = ord("}")  # the last record's closing bracket is of the wrong kind: TAPE_ERROR at that token, every string still valid
+
+    p = capi.DomParserImplementation(len(array_host) + 64)
+    s = torch.cuda.current_stream().cuda_stream
+
+    def resident(a):
+        buf = torch.from_numpy(np.concatenate([a, np.zeros(64, np.uint8)])).cuda()
+        idx = torch.zeros(len(a) + 16, dtype=torch.int32, device="cuda")
+        assert p.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, s) == 0
+        n, flags, _ = p.result(s)
+        assert flags == 0, flags
+        return buf, idx, n
+
+    sbuf_cap = 5 * (len(array_host) // 3) + 256
+    sbuf = torch.empty(sbuf_cap, dtype=torch.uint8, device="cuda")
+    b_stream, i_stream, n_stream = resident(stream_host)
+    b_array, i_array, n_array = resident(array_host)
+    b_broken, i_broken, n_broken = resident(broken_host)
+    tape_cap = min(4 * n_stream, len(stream_host) + 3 * (lines + 1)) + 8
+    tape = torch.empty(max(tape_cap, len(array_host) + 8), dtype=torch.int64, device="cuda")
+    table = torch.empty((lines + 2) * 4, dtype=torch.int32, device="cuda")
+
+    def run_many(buf=b_stream, idx=i_stream, n=n_stream, length=len(stream_host)):
+        return p.stage2_many_device(buf.data_ptr(), length, idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf_cap, table.data_ptr(), lines + 2, stream=s)
+
+    def run_single():
+        return p.stage2_device(b_array.data_ptr(), len(array_host), i_array.data_ptr(), n_array, tape.data_ptr(), len(array_host) + 8, sbuf.data_ptr(), sbuf_cap, stream=s)
+
+    def run_broken():
+        return run_many(b_broken, i_broken, n_broken, len(broken_host))
+
+    # the two roads deliver the same words: an array adds its two brackets to the records' words, a stream two root words per record
+    code, docs, tw_many, sb_many = run_many()
+    assert (code, docs) == (0, lines), (code, docs, lines)
+    code1, tw_single, sb_single = run_single()
+    assert code1 == 0 and tw_many == (tw_single - 4) + 2 * lines and sb_many == sb_single, (code1, tw_many, tw_single, sb_many, sb_single)
+    codeb, docsb, _, _ = run_broken()
+    assert (codeb, docsb) == (3, lines - 1), (codeb, docsb)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    for _ in range(args.warmup):
+        run_many(), run_single(), run_broken()
+    t_many, t_single, t_broken = [], [], []
+    for k in range(args.reps):  # alternating: what the clock and the neighbours do hits all three alike
+        t_many.append(timed(run_many))
+        t_single.append(timed(run_single))
+        if k % 4 == 0:
+            t_broken.append(timed(run_broken))
+    out = {"mib": round(len(stream_host) / 2 ** 20, 1), "records": int(lines), "tokens_stream": int(n_stream), "tokens_array": int(n_array), "tape_words_stream": int(tw_many),
+           "tape_words_array": int(tw_single), "string_bytes": int(sb_many), "reps": args.reps,
+           "a_stream_ms": {"median": round(statistics.median(t_many), 3), "min": round(min(t_many), 3), "max": round(max(t_many), 3)},
+           "b_array_ms": {"median": round(statistics.median(t_single), 3), "min": round(min(t_single), 3), "max": round(max(t_single), 3)},
+           "ratio_a_over_b": round(statistics.median(t_many) / statistics.median(t_single), 3),
+           "d_broken_last_record_ms": {"median": round(statistics.median(t_broken), 3), "reps": len(t_broken)}}
+    if not args.no_cpu and os.path.exists(_paths.LIB_REF):
+        R = ctypes.CDLL(_paths.LIB_REF)
+        R.sjref_available.restype = ctypes.c_int
+        R.sjref_available.argtypes = [ctypes.c_char_p]
+        R.sjref_bench_stage2.restype = ctypes.c_double
+        R.sjref_bench_stage2.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        impl = next((i for i in (b"icelake", b"haswell", b"westmere") if R.sjref_available(i)), None)
+        if impl:
+            padded = np.concatenate([array_host, np.zeros(128, np.uint8)])
+            err = ctypes.c_int(0)
+            sec = R.sjref_bench_stage2(impl, padded.ctypes.data, len(array_host), 2, ctypes.byref(err))
+            out["c_reference_stage2_ms"] = {"value": round(sec * 1e3, 1), "kernel": impl.decode(), "cores": 1, "error": err.value, "sample": "best of 2"}
+    else:
+        out["c_reference_stage2_ms"] = "not measured"
+    p.close()
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -44,6 +44,12 @@ class Doc(ctypes.Structure):
                 ("n", ctypes.c_uint32), ("error", ctypes.c_int)]
 
 
+# what include/sjgpu_stream.h declares (document streams: an extension of the C-ABI with a header of its own)
+STREAM_EXPORTS = ["sjgpu_stage2_many_device", "sjgpu_parse_many"]
+# sjgpu_doc_span (include/sjgpu_stream.h): one entry of the document table of sjgpu_stage2_many_device / sjgpu_parse_many
+DOC_SPAN = np.dtype([("first_token", np.uint32), ("byte_begin", np.uint32), ("tape_begin", np.uint32), ("string_begin", np.uint32)])
+
+
 class ScanResult(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
 
@@ -129,6 +135,10 @@ def load_library():
     L.sjgpu_match_keys_device.argtypes = [vp, vp, sz, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, u32p]
     L.sjgpu_parse.restype = ctypes.c_int
     L.sjgpu_parse.argtypes = [vp, vp, sz, ctypes.c_uint32, vp, sz, vp, sz, u64p, u64p]
+    L.sjgpu_stage2_many_device.restype = ctypes.c_int
+    L.sjgpu_stage2_many_device.argtypes = [vp, vp, sz, vp, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp, sz, vp, sz, vp, u32p, u64p, u64p]
+    L.sjgpu_parse_many.restype = ctypes.c_int
+    L.sjgpu_parse_many.argtypes = [vp, vp, sz, ctypes.c_uint32, vp, sz, vp, sz, vp, sz, u32p, u64p, u64p]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int
@@ -429,6 +439,34 @@ class DomParserImplementation:
         if rc < 0:
             raise SjgpuError(f"sjgpu_parse error {rc}: {self.last_error()}")
         return rc, tape[: tw.value], sbuf[: sb.value]
+
+    def stage2_many_device(self, buf_ptr, length, idx_ptr, n, tape_ptr, tape_cap_words, strbuf_ptr, strbuf_bytes, docs_ptr, doc_cap, max_depth=1024, stream=0):
+        """sjgpu_stage2_many_device: the tapes of a document stream, one per document (docs_ptr: doc_cap entries of DOC_SPAN on the device)
+        -> (simdjson error_code of the first broken document or 0, documents delivered, tape words, string buffer bytes); raises on infrastructure errors"""
+        docs, tw, sb = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = self.L.sjgpu_stage2_many_device(self.h, buf_ptr, int(length), idx_ptr, int(n), int(max_depth), tape_ptr, int(tape_cap_words), strbuf_ptr, int(strbuf_bytes),
+                                             docs_ptr, int(doc_cap), stream or None, ctypes.byref(docs), ctypes.byref(tw), ctypes.byref(sb))
+        if rc < 0:
+            raise SjgpuError(f"sjgpu_stage2_many_device error {rc}: {self.last_error()}")
+        return rc, int(docs.value), int(tw.value), int(sb.value)
+
+    def parse_many(self, data, max_depth=1024):
+        """sjgpu_parse_many for a host buffer that holds a stream of documents: (error_code of the first broken document or 0, documents delivered,
+        [(tape, string_buf) views per document], the raw arrays (tape, string_buf, table as a DOC_SPAN array of documents + 1 entries))"""
+        a = _as_u8(data)
+        tape = np.zeros(4 * len(a) + 8, dtype=np.uint64)  # (4 words per token always suffice, and a token is at least one byte)
+        sbuf = np.zeros(5 * (len(a) // 3) + 256, dtype=np.uint8)
+        table = np.zeros(len(a) + 2, dtype=DOC_SPAN)
+        docs, tw, sb = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = self.L.sjgpu_parse_many(self.h, a.ctypes.data if len(a) else None, len(a), int(max_depth), tape.ctypes.data, len(tape), sbuf.ctypes.data, len(sbuf),
+                                     table.ctypes.data, len(table), ctypes.byref(docs), ctypes.byref(tw), ctypes.byref(sb))
+        if rc < 0:
+            raise SjgpuError(f"sjgpu_parse_many error {rc}: {self.last_error()}")
+        d = int(docs.value)
+        table = table[: d + 1] if d else table[:0]
+        views = [(tape[int(table["tape_begin"][k]): int(table["tape_begin"][k + 1])], sbuf[int(table["string_begin"][k]): int(table["string_begin"][k + 1])])
+                 for k in range(d)]
+        return rc, d, views, (tape[: tw.value], sbuf[: sb.value], table)
 
     def result(self, stream=0):  # waits for `stream`
         r = ScanResult()

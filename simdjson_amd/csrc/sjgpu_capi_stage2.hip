@@ -1,6 +1,7 @@
-// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, what follows the structural list on the device: the strings of a document, On-Demand's raw
-// key comparison, stage 2 (the DOM tape) and sjgpu_parse.  Shared with the other units: sjgpu_ctx.h.
+// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h and include/sjgpu_stream.h, what follows the structural list on the device: the strings of a document, On-Demand's raw
+// key comparison, stage 2 (the DOM tape of a document, the tapes of a document stream), sjgpu_parse and sjgpu_parse_many.  Shared with the other units: sjgpu_ctx.h.
 #include "sjgpu_ctx.h"
+#include "sjgpu_stream.h"
 
 extern "C" {
 
@@ -137,6 +138,168 @@ int sjgpu_stage2_tokens_device(sjgpu_ctx *ctx, const void *buf_dev, size_t len, 
   if (tape_words_out) { *tape_words_out = ht.tape_words; }
   if (string_bytes_out) { *string_bytes_out = hs.bytes; }
   return 0;
+}
+
+// ---- stage 2 of a document stream: one tape per document (sjgpu_tape_many.hip) --------------------------------------------------------------
+// One run over idx[0 .. n) of buf[0 .. len): the token front, the string pass, the STREAM tape into workspace, the document ordinals.  The results come
+// back in one copy; the optimistic roads (string stream alone, the sort in one pass) are repeated like sjgpu_stage2_device repeats them.
+namespace {
+struct many_run {
+  tape_result_dev ht;
+  strings_result_dev hs;
+  many_result_dev hm;
+  many_workspace mw;
+  tape_stream_view view;
+  strings_result_dev *sres;
+};
+int run_many(sjgpu_ctx *ctx, const uint8_t *buf, size_t len, const uint32_t *idx, uint32_t n, uint32_t max_depth, uint8_t *string_buf, size_t string_buf_bytes,
+             hipStream_t s, many_run *r) {
+  // [strings result 32 B, padded to 256][scratch of the string pass][string offsets, n + 1 words][tape workspace][flat tape, ordinals, record starts]
+  const size_t scratch_at = 256, scratch = strings_scratch_bytes(n, len), offs_at = scratch_at + scratch;
+  const size_t tape_at = (offs_at + (size_t(n) + 1) * sizeof(uint32_t) + 255) & ~size_t(255);
+  const size_t many_at = (tape_at + tape_workspace_bytes(n, len) + 255) & ~size_t(255);
+  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_stage2), &ctx->d_stage2_bytes, many_at + many_workspace_bytes(n, len));
+  if (rc) { return rc; }
+  uint8_t *ws = ctx->d_stage2;
+  // the tape workspace's first slot of 256 bytes, cleared by k_tape_init: [0] the tape's result, [64] the strings', [96] this unit's -- one copy of 128 bytes
+  r->sres = reinterpret_cast<strings_result_dev *>(ws + tape_at + 64);
+  many_result_dev *mres = reinterpret_cast<many_result_dev *>(ws + tape_at + 96);
+  static_assert(sizeof(strings_result_dev) <= 32 && sizeof(many_result_dev) <= 32, "the slots of the result block");
+  uint32_t *offsets = reinterpret_cast<uint32_t *>(ws + offs_at);
+  r->mw = carve_many_workspace(ws + many_at, n);
+  r->view = tape_workspace_view(ws + tape_at, n, len);
+  int roads = STRINGS_STREAM_ONLY;
+  bool deep = false;
+  for (;;) {
+    const int *string_tokens = launch_tape_front(buf, len, idx, n, max_depth, ws + tape_at, s, nullptr);
+    const strings_handoff strs = launch_parse_strings(buf, len, idx, n, false, string_buf, string_buf_bytes, offsets, r->sres, ws + scratch_at, s, string_tokens, roads);
+    launch_tape_stream(buf, len, idx, n, max_depth, offsets, strs, string_buf, r->mw.flat_tape, r->mw.flat_cap, ws + tape_at, s, deep, r->mw.doc_ord, r->mw.doc_str);
+    launch_many_ordinals(idx, n, r->mw, r->view, r->sres, mres, s);
+    SJ_TRY(ctx, hipGetLastError());
+    uint8_t *const pinned = reinterpret_cast<uint8_t *>(ctx->h_result);
+    SJ_TRY(ctx, hipMemcpyAsync(pinned + 64, ws + tape_at, 128, hipMemcpyDeviceToHost, s));
+    SJ_TRY(ctx, hipStreamSynchronize(s));
+    memcpy(&r->ht, pinned + 64, sizeof(r->ht));
+    memcpy(&r->hs, pinned + 128, sizeof(r->hs));
+    memcpy(&r->hm, pinned + 160, sizeof(r->hm));
+    bool again = false;
+    if (roads == STRINGS_STREAM_ONLY && r->hs.path == 2 && !r->hs.overflow) { roads = STRINGS_WALK_ONLY; again = true; }
+    if (!deep && r->ht.max_level >= TAPE_ONE_PASS_LEVELS) { deep = true; again = true; }
+    if (!again) { break; }
+  }
+  ctx->last_string_path = r->hs.path;
+  return 0;
+}
+} // namespace
+
+int sjgpu_stage2_many_device(sjgpu_ctx *ctx, const void *buf_dev, size_t len, const void *idx_dev, uint32_t n, uint32_t max_depth, void *tape_dev,
+                             size_t tape_cap_words, void *string_buf_dev, size_t string_buf_bytes, void *docs_dev, size_t doc_cap, void *stream,
+                             uint32_t *docs_out, uint64_t *tape_words_out, uint64_t *string_bytes_out) {
+  if (docs_out) { *docs_out = 0; }
+  if (tape_words_out) { *tape_words_out = 0; }
+  if (string_bytes_out) { *string_bytes_out = 0; }
+  if (!ctx || !buf_dev || !idx_dev || !tape_dev || !string_buf_dev || !docs_dev || max_depth == 0 || max_depth > 4095u) { return SJGPU_E_BADARG; }
+  if ((reinterpret_cast<uintptr_t>(buf_dev) & 15u) || (reinterpret_cast<uintptr_t>(tape_dev) & 7u) || (reinterpret_cast<uintptr_t>(idx_dev) & 3u) ||
+      (reinterpret_cast<uintptr_t>(docs_dev) & 15u)) { return SJGPU_E_BADARG; }
+  if (n == 0) { return E_EMPTY; } // walk_document: at_eof() (json_iterator.h:126)
+  if (len > 2400000000ull || n >= 0xFFFFFFF0u) { return E_CAPACITY; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick(ctx, stream);
+  const uint8_t *buf = static_cast<const uint8_t *>(buf_dev);
+  const uint32_t *idx = static_cast<const uint32_t *>(idx_dev);
+  many_run r;
+  int rc = run_many(ctx, buf, len, idx, n, max_depth, static_cast<uint8_t *>(string_buf_dev), string_buf_bytes, s, &r);
+  if (rc) { return rc; }
+  int code = 0;
+  uint32_t n_run = n;
+  if (r.hm.has_error) {
+    // document_stream stops at the first broken document.  Its code is the smallest error key of the whole list; what is delivered is the list in front of
+    // the document that holds that key -- run again, because a stray bracket behind the error may have paired with a bracket of an earlier document.
+    uint64_t key = r.ht.error_key;
+    if (r.hs.first_bad != 0xFFFFFFFFu) {
+      const uint64_t sk = (uint64_t(r.hs.first_bad) << 8) | (2u << 4) | 5u; // STRING_ERROR
+      if (sk < key) { key = sk; }
+    }
+    code = int(key & 0xFu);
+    n_run = r.hm.cut_token;
+    if (n_run == 0) { return code; } // the first document is the broken one
+    const size_t len_run = r.hm.cut_byte; // idx[n_run]: the prefix ends where its sentinel would stand
+    rc = run_many(ctx, buf, len_run, idx, n_run, max_depth, static_cast<uint8_t *>(string_buf_dev), string_buf_bytes, s, &r);
+    if (rc) { return rc; }
+    if (r.hm.has_error) { return E_UNEXPECTED; } // (a prefix of complete documents in front of the first error is valid)
+  }
+  if (r.hs.overflow || r.ht.overflow) { return SJGPU_E_OVERFLOW; }
+  const uint32_t docs = r.hm.docs;
+  const uint64_t total = r.ht.tape_words + 2ull * docs;
+  if (total > 0x7FFFFFFFull) { return E_CAPACITY; } // tape positions are 31 bits
+  if (size_t(docs) + 1 > doc_cap) {
+    if (docs_out) { *docs_out = docs + 1; } // the entries the table needs
+    return SJGPU_E_OVERFLOW;
+  }
+  if (total > tape_cap_words) { return SJGPU_E_OVERFLOW; }
+  launch_many_relocate(idx, n_run, docs, total, r.mw, r.view, r.sres, static_cast<doc_span_dev *>(docs_dev), static_cast<uint64_t *>(tape_dev), s);
+  SJ_TRY(ctx, hipGetLastError());
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  if (docs_out) { *docs_out = docs; }
+  if (tape_words_out) { *tape_words_out = total; }
+  if (string_bytes_out) { *string_bytes_out = r.hs.bytes; }
+  return code;
+}
+
+int sjgpu_parse_many(sjgpu_ctx *ctx, const uint8_t *buf, size_t len, uint32_t max_depth, uint64_t *tape_out, size_t tape_cap_words, uint8_t *string_buf_out,
+                     size_t string_buf_bytes, sjgpu_doc_span *docs_out_host, size_t doc_cap, uint32_t *docs_out, uint64_t *tape_words_out,
+                     uint64_t *string_bytes_out) {
+  if (docs_out) { *docs_out = 0; }
+  if (tape_words_out) { *tape_words_out = 0; }
+  if (string_bytes_out) { *string_bytes_out = 0; }
+  if (!ctx || !tape_out || !string_buf_out || !docs_out_host) { return SJGPU_E_BADARG; }
+  if (len > ctx->capacity) { return E_CAPACITY; }
+  if (len == 0) { return E_EMPTY; }
+  if (!buf) { return SJGPU_E_BADARG; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_staging_in(ctx, len);
+  if (rc) { return rc; }
+  size_t idx_bytes = ctx->d_idx_words * sizeof(uint32_t);
+  rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_idx), &idx_bytes, (grown(len) + 16) * sizeof(uint32_t));
+  ctx->d_idx_words = idx_bytes / sizeof(uint32_t);
+  if (rc) { return rc; }
+  hipStream_t s = ctx->stream;
+  SJ_TRY(ctx, hipMemcpyAsync(ctx->d_in, buf, len, hipMemcpyHostToDevice, s));
+  sjgpu_scan_result res{0, 0, 0};
+  for (int attempt = 0; attempt < 2; attempt++) { // a single-pass scan that gives up is re-run on the split pipeline
+    enqueue_stage1(ctx, use_fused(ctx, len, 0) && attempt == 0, ctx->d_in, len, ctx->d_idx, ctx->d_idx_words, s, nullptr);
+    SJ_ENQUEUED(ctx);
+    rc = fetch_result(ctx, s, &res);
+    if (rc) { return rc; }
+    if (!(res.flags & SJGPU_F_INTERNAL)) { break; }
+  }
+  if (res.flags & (SJGPU_F_INTERNAL | SJGPU_F_IDX_OVERFLOW)) { return E_UNEXPECTED; }
+  const int e1 = sjgpu_stage1_error_from_flags(res.n, res.flags); // (the errors of stage 1 concern the whole buffer and come first)
+  if (e1) { return e1; }
+  // [tapes: 4 n words always suffice, and so do len + 3 n (len + 3 per document)][table: n + 1 entries][string records]
+  const size_t tape_words_cap = (size_t(res.n) < len ? 4 * size_t(res.n) : len + 3 * size_t(res.n)) + 8, table_at = tape_words_cap * sizeof(uint64_t), table_cap = size_t(res.n) + 1;
+  const size_t str_at = (table_at + table_cap * sizeof(sjgpu_doc_span) + 255) & ~size_t(255), str_cap = 5 * (len / 3) + 256;
+  rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_doc), &ctx->d_doc_bytes, str_at + str_cap);
+  if (rc) { return rc; }
+  uint64_t tw = 0, sb = 0;
+  uint32_t docs = 0;
+  const int code = sjgpu_stage2_many_device(ctx, ctx->d_in, len, ctx->d_idx, res.n, max_depth, ctx->d_doc, tape_words_cap, ctx->d_doc + str_at, str_cap,
+                                            ctx->d_doc + table_at, table_cap, s, &docs, &tw, &sb);
+  if (code < 0) { return code; }
+  if (docs == 0) { return code; } // nothing delivered (the first document is broken)
+  if (tw > tape_cap_words || sb > string_buf_bytes) { return SJGPU_E_OVERFLOW; }
+  if (size_t(docs) + 1 > doc_cap) {
+    if (docs_out) { *docs_out = docs + 1; }
+    return SJGPU_E_OVERFLOW;
+  }
+  SJ_TRY(ctx, hipMemcpyAsync(tape_out, ctx->d_doc, tw * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  if (sb) { SJ_TRY(ctx, hipMemcpyAsync(string_buf_out, ctx->d_doc + str_at, sb, hipMemcpyDeviceToHost, s)); }
+  SJ_TRY(ctx, hipMemcpyAsync(docs_out_host, ctx->d_doc + table_at, (size_t(docs) + 1) * sizeof(sjgpu_doc_span), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  if (docs_out) { *docs_out = docs; }
+  if (tape_words_out) { *tape_words_out = tw; }
+  if (string_bytes_out) { *string_bytes_out = sb; }
+  return code;
 }
 
 int sjgpu_parse(sjgpu_ctx *ctx, const uint8_t *buf, size_t len, uint32_t max_depth, uint64_t *tape_out, size_t tape_cap_words, uint8_t *string_buf_out,

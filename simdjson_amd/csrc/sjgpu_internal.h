@@ -240,6 +240,49 @@ const int *launch_tape_front(const uint8_t *buf, uint64_t len, const uint32_t *i
 // a tape that is NOT valid: the caller runs the three launches again with deep = true (sjgpu_stage2_device: optimistic, five launches saved on nearly every call).
 void launch_tape(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, uint32_t max_depth, const uint32_t *str_offsets, strings_handoff strs,
                  uint8_t *string_buf, uint64_t *tape, uint64_t tape_cap, void *workspace, hipStream_t s, bool deep = true);
+// ---- the tapes of a document stream (sjgpu_tape_many.hip: sjgpu_stage2_many_device) --------------------------------------------------------------
+// launch_tape over a list that holds one document after the other (walk_document<STREAMING = true>): the FLAT tape -- word k of the whole list at
+// flat_tape[k + 1], bracket payloads in those coordinates, no root words; room for 2 n + 2 words always suffices --, doc_flag[0 .. n] (1: the token has
+// depth 0 in front of it and begins a document; the sentinel: 0) and doc_str[i], written for the tokens that carry a flag only: where the string records
+// of their document begin.  res->tape_words = the words of the tokens alone.  launch_tape_front is the single document's.
+void launch_tape_stream(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, uint32_t max_depth, const uint32_t *str_offsets, strings_handoff strs,
+                        uint8_t *string_buf, uint64_t *flat_tape, uint64_t flat_cap, void *workspace, hipStream_t s, bool deep, int *doc_flag, uint32_t *doc_str);
+// what the relocation reads of the tape workspace once launch_tape_stream has run: tokc[i + 2] = byte of token i, tpos[0 .. n] = flat tape positions,
+// the result, and the device word that holds n + 1 (the length of a scan over per-token arrays)
+struct tape_stream_view {
+  const uint8_t *tokc;
+  const int *tpos;
+  tape_result_dev *res;
+  const uint32_t *n_plus_1;
+};
+tape_stream_view tape_workspace_view(void *workspace, uint32_t n, uint64_t len);
+// One entry of the document table (include/sjgpu_stream.h: sjgpu_doc_span, the same four words)
+struct doc_span_dev {
+  uint32_t first_token, byte_begin, tape_begin, string_begin;
+};
+// what one run over the list leaves for the host, 16 bytes: the documents the list holds, and -- when the tape's or the strings' result carries an
+// error -- the first token of the document that holds the offending list index and its byte offset (a cut between two documents)
+struct many_result_dev {
+  uint32_t docs, cut_token, cut_byte, has_error;
+};
+struct many_workspace {
+  uint64_t *flat_tape; // 2 n + 4 words
+  int *doc_ord;        // n + 1: the flags, then (scanned in place) the documents that begin in front of token i
+  uint32_t *doc_str;   // n + 1
+  int *partial;        // the scan's block sums
+  size_t flat_cap, bytes;
+};
+many_workspace carve_many_workspace(void *base, uint32_t n);
+size_t many_workspace_bytes(uint32_t n, uint64_t len);
+// behind launch_tape_stream: doc_ord becomes the exclusive scan of the flags; *out = the number of documents and, from the smaller of the two results'
+// error keys, the cut in front of the broken document
+void launch_many_ordinals(const uint32_t *idx, uint32_t n, const many_workspace &m, const tape_stream_view &v, const strings_result_dev *sres, many_result_dev *out,
+                          hipStream_t s);
+// behind that, for a run WITHOUT an error and with room for everything (docs + 1 table entries, flat words + 2 docs tape words): the document table and
+// the tapes, document by document
+// (docs, total_words: what the host read back -- the table has docs + 1 entries, nothing is written at or beyond tape[total_words]; table: 16-byte aligned)
+void launch_many_relocate(const uint32_t *idx, uint32_t n, uint32_t docs, uint64_t total_words, const many_workspace &m, const tape_stream_view &v,
+                          const strings_result_dev *sres, doc_span_dev *table, uint64_t *tape, hipStream_t s);
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);

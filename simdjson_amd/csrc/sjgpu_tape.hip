@@ -563,12 +563,19 @@ __global__ __launch_bounds__(1024) void k_tok_scan_sums(int *__restrict__ sums, 
 // and commas go straight into the sort's input with
 // their level: the depth in front of an opening bracket, the depth behind a closing one, and that of the container a comma separates
 // the members of -- clamped to [0, kmax] (beyond the nesting limit an error is already certain); *m_out = how many went in
+// STREAM (sjgpu_stage2_many_device: the list holds one document after the other, walk_document<STREAMING = true>, json_iterator.h:120-244): a token with
+// depth 0 in front of it is the ROOT of the next document, not "more than one value at the root" (:237-240) -- `first` of the two rules is d == 0 --
+// and says so: doc_flag[i] = 1 (i <= n; the sentinel: 0) and, for such a token, doc_str[i] = where the string records of its document begin.  The tape
+// this variant leaves is FLAT: no root words, positions of the whole list (sjgpu_tape_many.hip relocates it document by document).  Token 0 keeps its root
+// contribution to the counters, as k_tok_stage counted it; the later roots take the inner one -- they differ for bytes that are no value at the root
+// only, and those are this very token's TAPE_ERROR (rank 0), behind which nothing is promised.
+template <bool STREAM>
 __global__ __launch_bounds__(TS_THREADS, 4) void k_tok_apply(const u8 *__restrict__ tokc, u32 n, u32 kmax, u32 max_depth, const int *__restrict__ sums, u32 nblocks,
                                                          int *__restrict__ tpos, unsigned short *__restrict__ key, u32 *__restrict__ tok,
                                                          int *__restrict__ m_out, int *__restrict__ max_level, const u64 *__restrict__ numbits,
                                                          const u8 *__restrict__ numtype, const u32 *__restrict__ str_offsets, strings_handoff strs,
                                                          u8 *__restrict__ string_buf, u64 *__restrict__ tape, u64 tape_cap, tape_result_dev *__restrict__ res,
-                                                         const u32 *__restrict__ entry_tab) {
+                                                         const u32 *__restrict__ entry_tab, int *__restrict__ doc_flag, u32 *__restrict__ doc_str) {
   // Round 4, second half: the nesting depth is not written anywhere.  What it decides -- "the root value has ended" and the nesting limit
   // (depth_rule, sj_tape_rules.h) and "the list ends inside a container" -- is said HERE, where it sits in a register; the levels of the brackets and
   // commas go into the sort's keys as before.  (k_tape_rules read 4 B per token for it, this kernel wrote them.)
@@ -635,6 +642,7 @@ __global__ __launch_bounds__(TS_THREADS, 4) void k_tok_apply(const u8 *__restric
     __syncthreads();
     if (i0 <= n) {
       int tp[4];
+      int starts[4] = {0, 0, 0, 0}; // STREAM: the token begins a document
       // where the records of this thread's string tokens begin: its (at most four) strings have consecutive ordinals, so the five words are
       // requested HERE, all at once, not one by one inside the loop below (as dependent loads they made this kernel 120 us longer than the
       // separate pass over a list of string tokens had been: profiles/r04_tape_kernel_stats.txt)
@@ -669,18 +677,25 @@ __global__ __launch_bounds__(TS_THREADS, 4) void k_tok_apply(const u8 *__restric
         const u32 ch = (four >> (8u * j)) & 0xFFu, c1 = j < 3 ? (four >> (8u * (j + 1))) & 0xFFu : behind2 & 0xFFu;
         const int d = depth0 + int(eb >> 16) - int(ec & 0xFFFFu);
         tp[j] = slots0 + int(ea & 0xFFFFu);
+        const bool first = STREAM ? d == 0 : i == 0; // the root token (of this document)
         {
           u32 rank = 0, rank_self = 0;
-          u32 g = live ? depth_rule(i == 0, ch, i + 1 < n ? c1 : 0u, d, max_depth, &rank) : 0u;
+          u32 g = live ? depth_rule(first, ch, i + 1 < n ? c1 : 0u, d, max_depth, &rank) : 0u;
           if (i == n && d != 0) { g = SJ_TAPE_ERROR; rank = 0; } // the walk meets the sentinel inside a container
           // what the token says about itself from the two tokens in front of it (the followers of a comma are judged by the comma: k_tape_match)
-          const u32 gs = live ? token_rule_self_entries(i == 0, x[j], j == 0 ? xm1 : x[j > 0 ? j - 1 : 0], j == 0 ? xm2 : (j == 1 ? xm1 : x[j > 1 ? j - 2 : 0]), &rank_self) : 0u;
+          const u32 gs = live ? token_rule_self_entries(first, x[j], j == 0 ? xm1 : x[j > 0 ? j - 1 : 0], j == 0 ? xm2 : (j == 1 ? xm1 : x[j > 1 ? j - 2 : 0]), &rank_self) : 0u;
           const u32 low_d = g ? (rank << 4) | g : 0xFFFFu, low_s = gs ? (rank_self << 4) | gs : 0xFFFFu, low = low_d < low_s ? low_d : low_s; // the smaller key of one token
           if (low != 0xFFFFu && err_low == 0u) { err_index = i; err_low = low; } // (a thread meets its tokens in list order: its first error is its smallest key)
         }
         const int strings_before = strs0 + int(eb & 0xFFFFu);
         const int slot = sel0 + int(ea >> 16);
         if (i == n) { *m_out = slot; m_out[3] = slot + 1; m_out[4] = strings_before; }
+        if constexpr (STREAM) {
+          if (live && first) { // (one token per document: the record start is a dependent load the other tokens do not pay for)
+            starts[j] = 1;
+            doc_str[i] = stream_strings ? strs.outq[u32(strings_before)] : str_offsets[i]; // (outq: n + 2 entries; the offsets are CSR: a token that is no string has the next record's)
+          }
+        }
         const u32 list = value_list_of(pj); // (of the packed contribution, not of the table entry: the root token's differs)
         const bool is_number = list == LIST_NUMBERS, is_string = list == LIST_STRINGS, is_rest = list == LIST_REST;
         const u32 at = u32(tp[j]) + 1u; // (tape positions are ints: below 2^31)
@@ -713,8 +728,12 @@ __global__ __launch_bounds__(TS_THREADS, 4) void k_tok_apply(const u8 *__restric
       }
       if (i0 + 3 <= n) {
         *reinterpret_cast<int4 *>(tpos + i0) = make_int4(tp[0], tp[1], tp[2], tp[3]);
+        if constexpr (STREAM) { *reinterpret_cast<int4 *>(doc_flag + i0) = make_int4(starts[0], starts[1], starts[2], starts[3]); }
       } else {
-        for (u32 j = 0; j < 4 && i0 + j <= n; j++) { tpos[i0 + j] = tp[j]; }
+        for (u32 j = 0; j < 4 && i0 + j <= n; j++) {
+          tpos[i0 + j] = tp[j];
+          if constexpr (STREAM) { doc_flag[i0 + j] = starts[j]; }
+        }
       }
     }
   }
@@ -858,22 +877,30 @@ struct sorted_pairs {
 // Four consecutive sorted elements per thread, the loads of each step of the chain (element -> its container's open -> that open's key and
 // payload) issued for all four before any is used: with one element per thread this kernel ran at the latency of its chain.  Rounds 3-4a had two more
 // steps -- the tape positions of the close and of its open, gathered from the per-token array, and a byte scattered (then: two gathered) per comma.
+// STREAM: the flat tape of a list of documents -- no root words, no comparison of the outer bracket with the list's last token (json_iterator.h:139-144 is
+// skipped by the streaming walk); res->tape_words = the words of the tokens alone.
 constexpr u32 TM_PER = 4;
+template <bool STREAM>
 __global__ __launch_bounds__(TP_THREADS) void k_tape_match(sorted_pairs sorted, const int *__restrict__ m_ptr, const int *__restrict__ opens_before,
                                                           const u32 *__restrict__ openpos, const int *__restrict__ tpos, const u8 *__restrict__ tokc, u32 n,
                                                           u64 *__restrict__ tape, u64 tape_cap, tape_result_dev *__restrict__ res) {
   if (blockIdx.x == 0 && threadIdx.x == 0) { // what belongs to no token (k_tape_rules' last thread, rounds 3-5): the root words, the sizes, the root container's end
     const u64 words = u64(u32(tpos[n])) + 2;
-    res->tape_words = words;
     res->max_level = u32(*sorted.max_level);
-    if (words <= tape_cap) {
-      tape[0] = tape_word('r', words);           // visit_document_end, tape_builder.h:160-165
-      tape[words - 1] = tape_word('r', 0);
+    if constexpr (STREAM) {
+      res->tape_words = words - 2;
+      if (words > tape_cap) { res->overflow = 1; } // (the flat tape keeps the single document's positions: word k of the list at [k + 1])
     } else {
-      res->overflow = 1;
+      res->tape_words = words;
+      if (words <= tape_cap) {
+        tape[0] = tape_word('r', words);           // visit_document_end, tape_builder.h:160-165
+        tape[words - 1] = tape_word('r', 0);
+      } else {
+        res->overflow = 1;
+      }
+      const u32 c0 = tokc[2], last = tokc[n + 1];
+      if ((c0 == '{' && last != '}') || (c0 == '[' && last != ']')) { report_error(res, error_key(0, 0, SJ_TAPE_ERROR)); } // json_iterator.h:138-143
     }
-    const u32 c0 = tokc[2], last = tokc[n + 1];
-    if ((c0 == '{' && last != '}') || (c0 == '[' && last != ']')) { report_error(res, error_key(0, 0, SJ_TAPE_ERROR)); } // json_iterator.h:138-143
   }
   const unsigned short *__restrict__ key = sorted.key();
   const u32 *__restrict__ tok = sorted.tok();
@@ -1053,14 +1080,15 @@ const int *launch_tape_front(const uint8_t *buf, uint64_t len, const uint32_t *i
 // launch_tape: the rest, behind the string pass.  str_offsets: what the per-string kernels left (n + 1 words), read when they wrote the buffer;
 // strs: where the records of the stream compaction begin, read when IT wrote the buffer (the flag decides on the device); string_buf: the
 // buffer, for the length words.
-void launch_tape(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, uint32_t max_depth, const uint32_t *str_offsets, strings_handoff strs,
-                 uint8_t *string_buf, uint64_t *tape, uint64_t tape_cap, void *workspace, hipStream_t s, bool deep) {
+template <bool STREAM>
+static void launch_tape_of(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, uint32_t max_depth, const uint32_t *str_offsets, strings_handoff strs,
+                           uint8_t *string_buf, uint64_t *tape, uint64_t tape_cap, void *workspace, hipStream_t s, bool deep, int *doc_flag, uint32_t *doc_str) {
   const tape_workspace w = carve(static_cast<uint8_t *>(workspace), n, len);
   const u32 n1 = n + 1;
   const int *m_ptr = w.m;
   const u32 kmax = max_depth < 4095u ? max_depth : 4095u;
-  hipLaunchKernelGGL(k_tok_apply, dim3(w.tok_blocks), dim3(TS_THREADS), 0, s, w.tokc, n, kmax, max_depth, w.sums, w.tok_blocks, w.slots, w.key_a, w.tok_a, w.m, w.m + 1,
-                     w.numbits, w.numtype, str_offsets, strs, string_buf, tape, tape_cap, w.res, w.entry_tab);
+  hipLaunchKernelGGL(k_tok_apply<STREAM>, dim3(w.tok_blocks), dim3(TS_THREADS), 0, s, w.tokc, n, kmax, max_depth, w.sums, w.tok_blocks, w.slots, w.key_a, w.tok_a, w.m, w.m + 1,
+                     w.numbits, w.numtype, str_offsets, strs, string_buf, tape, tape_cap, w.res, w.entry_tab, doc_flag, doc_str);
   // two passes of six bits cover levels up to 4095; the second one only runs for documents nested 64 deep and more
   const int *max_level = w.m + 1;
   hipLaunchKernelGGL(k_radix_hist, dim3(w.tiles), dim3(64), 0, s, w.key_a, m_ptr, 0u, w.tiles, w.hist, max_level, w.n_words + 1);
@@ -1075,8 +1103,22 @@ void launch_tape(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t
   // caller, who finds max_level in the result, comes back with deep = true)
   const sorted_pairs sorted{deep ? w.key_a : nullptr, w.key_b, deep ? w.tok_a : nullptr, w.tok_b, max_level};
   // containers: the ordinals came with the last scatter
-  hipLaunchKernelGGL(k_tape_match, dim3(blocks_of(n1, TP_THREADS * TM_PER)), dim3(TP_THREADS), 0, s, sorted, m_ptr, w.opens, w.openpos, w.slots, w.tokc, n, tape, tape_cap, w.res);
+  hipLaunchKernelGGL(k_tape_match<STREAM>, dim3(blocks_of(n1, TP_THREADS * TM_PER)), dim3(TP_THREADS), 0, s, sorted, m_ptr, w.opens, w.openpos, w.slots, w.tokc, n, tape, tape_cap, w.res);
   hipLaunchKernelGGL(k_tape_slow_numbers, dim3(64), dim3(64), 0, s, buf, len, idx, w.slots, w.slow_list, w.slow_cap, tape, tape_cap, w.res);
+}
+void launch_tape(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, uint32_t max_depth, const uint32_t *str_offsets, strings_handoff strs,
+                 uint8_t *string_buf, uint64_t *tape, uint64_t tape_cap, void *workspace, hipStream_t s, bool deep) {
+  launch_tape_of<false>(buf, len, idx, n, max_depth, str_offsets, strs, string_buf, tape, tape_cap, workspace, s, deep, nullptr, nullptr);
+}
+// The same over a list that holds one document after the other (sjgpu_tape_many.hip): the FLAT tape -- word k of the list at flat_tape[k + 1], bracket
+// payloads in those coordinates, no root words --, doc_flag[0 .. n] (1: the token begins a document) and doc_str (the record start of such a token).
+void launch_tape_stream(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, uint32_t max_depth, const uint32_t *str_offsets, strings_handoff strs,
+                        uint8_t *string_buf, uint64_t *flat_tape, uint64_t flat_cap, void *workspace, hipStream_t s, bool deep, int *doc_flag, uint32_t *doc_str) {
+  launch_tape_of<true>(buf, len, idx, n, max_depth, str_offsets, strs, string_buf, flat_tape, flat_cap, workspace, s, deep, doc_flag, doc_str);
+}
+tape_stream_view tape_workspace_view(void *workspace, uint32_t n, uint64_t len) {
+  const tape_workspace w = carve(static_cast<uint8_t *>(workspace), n, len);
+  return tape_stream_view{w.tokc, w.slots, w.res, w.n_words};
 }
 
 } // namespace sjgpu
