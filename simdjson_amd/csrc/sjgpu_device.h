@@ -723,6 +723,13 @@ __device__ __forceinline__ chunk_masks scan_chunk(const u32 (&w)[16], wave_carry
 // =====================================================================================================
 // output: bitmap -> ascending u32 offsets, through a per-wave LDS window, leaving as 16-byte stores
 // =====================================================================================================
+// tests/test_kernels_emu.py: with SJGPU_SELFTEST_WIDE_TAIL the tail of every write-out below (emit_indices, emit_span, emit_bytes) leaves as one whole
+// 16-byte vector -- v_last rounded up -- and the exact-capacity run of the emulator must FAIL with an overrun.  Without the define the factor is zero.
+#ifdef SJGPU_SELFTEST_WIDE_TAIL
+constexpr u32 SJGPU_TAIL_ROUND_UP = 1;
+#else
+constexpr u32 SJGPU_TAIL_ROUND_UP = 0;
+#endif
 constexpr u32 EMIT_WINDOW = 1536; // offsets per window (multiple of 4); denser chunks take several rounds
 // LDS words a window needs: + skew so that LDS slot and destination agree modulo 16 bytes, + a dump slot where
 // empty extraction chains park their (ignored) stores
@@ -814,7 +821,7 @@ __device__ __forceinline__ void emit_indices(u64 structural, u32 pos32, u32 lane
     const u32 here = min(EMIT_WINDOW, total - w0);
     u32 *const g0 = idx + (u64(base) + w0 - skew); // 16-byte aligned
     const u32 end = skew + here;                   // stage slots [skew, end) are live
-    const u32 v_first = (skew + 3u) >> 2, v_last = end >> 2; // whole 4-word vectors [v_first, v_last)
+    const u32 v_first = (skew + 3u) >> 2, v_last = (end + SJGPU_TAIL_ROUND_UP * 3u) >> 2; // whole 4-word vectors [v_first, v_last)
     if (v_last > v_first) {
 #pragma unroll 1
       for (u32 v = v_first + lane; v < v_last; v += 64) {
@@ -931,7 +938,7 @@ __device__ __forceinline__ bool emit_span(const u64 *m, u32 pos0, u32 lane, u32 
   wave_lds_fence();
   u32 *const g0 = idx + (u64(base) - skew); // 16-byte aligned
   const u32 end = skew + total;            // stage slots [skew, end) are live
-  const u32 v_first = (skew + 3u) >> 2, v_last = end >> 2;
+  const u32 v_first = (skew + 3u) >> 2, v_last = (end + SJGPU_TAIL_ROUND_UP * 3u) >> 2;
   if (v_last > v_first) {
 #pragma unroll 1
     for (u32 q = v_first + lane; q < v_last; q += 64) {
@@ -1023,7 +1030,7 @@ __device__ __forceinline__ void emit_bytes(const u32 (&w)[16], u64 keep, u32 lan
   wave_lds_fence();
   u8 *const g0 = dst + (u64(base) - skew);
   const u32 end = skew + total;
-  const u32 v_first = (skew + 15u) >> 4, v_last = end >> 4; // whole 16-byte vectors [v_first, v_last)
+  const u32 v_first = (skew + 15u) >> 4, v_last = (end + SJGPU_TAIL_ROUND_UP * 15u) >> 4; // whole 16-byte vectors [v_first, v_last)
   if (v_last > v_first) {
 #pragma unroll 1
     for (u32 v = v_first + lane; v < v_last; v += 64) {

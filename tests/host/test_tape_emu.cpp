@@ -4,6 +4,8 @@
 // (oracle/sj_oracle_stage2.c, pinned against the reference's dom::parser::parse): the error code always, every tape word and every byte of the
 // string buffer when the document is valid.  tests/host/test_tape_model.cpp checks the construction; this checks the kernels as written (block and
 // tile boundaries, the scans, the sort, look-backs, LDS hand-overs).  What is left to the GPU tier is what hipcc and the hardware make of them.
+// Every valid document then runs three more times: with exactly the tape words and string bytes the oracle delivered (the identical result), and with
+// each of the two one short (overflow) -- and the 0x5A fill behind the capacity given must be intact each time.
 // Input on stdin: [u32 length][bytes] records.  Usage: test_tape_emu [max_depth] [string road: 0 = as decided, 1 = per-string kernels forced]
 #include "sjgpu.h"
 #include "sjgpu_internal.h"
@@ -28,7 +30,7 @@ int main(int argc, char **argv) {
   const int force_walk = argc > 2 ? atoi(argv[2]) : 0;
   sj_emu::max_concurrent_workgroups = 4;
   if (force_walk) { setenv("SJGPU_STRING_STREAM", "0", 1); } // launch_parse_strings reads the switch per call
-  unsigned long docs = 0, valid = 0, codes[32] = {0}, roads[3] = {0, 0, 0}, reruns = 0;
+  unsigned long docs = 0, valid = 0, codes[32] = {0}, roads[3] = {0, 0, 0}, reruns = 0, capacity_runs = 0, deep_capacity_runs = 0;
   std::vector<uint8_t> doc_store, ws_store, tape_store, sbuf_store, idx_store;
   for (;;) {
     uint32_t len;
@@ -177,11 +179,66 @@ int main(int argc, char **argv) {
                   (unsigned long long)hs.bytes, (unsigned long long)sb, k, hs.path, docs, len, int(len > 300 ? 300 : len), (const char *)doc);
           return 1;
         }
+        // ---- the capacities put to the test: the same three launches with a tape of exactly tw words and a string buffer of exactly sb bytes (SUCCESS, the
+        // identical result), then with each of the two one short (overflow), the roads this document took kept.  The 0x5A fill behind the capacity GIVEN must
+        // be intact every time: a call that overflows keeps to its arrays too.
+        for (int leg = 0; leg < 3; leg++) {
+          if (leg == 2 && sb == 0) { continue; } // (a document without strings has no string capacity to fall short of)
+          const size_t tcap = size_t(tw) - (leg == 1), scap = size_t(sb) - (leg == 2);
+          uint64_t *tape2 = static_cast<uint64_t *>(aligned(tape_store, tape_cap * 8, 0x5A));
+          uint8_t *sbuf2 = static_cast<uint8_t *>(aligned(sbuf_store, str_cap, 0x5A));
+          strings_result_dev hs2;
+          tape_result_dev ht2;
+          int roads2 = STRINGS_STREAM_ONLY;
+          bool deep2 = false;
+          for (;;) {
+            const int *string_tokens = launch_tape_front(doc, len, idx, n, max_depth, ws + tape_at, nullptr);
+            const strings_handoff strs = launch_parse_strings(doc, len, idx, n, false, sbuf2, scap, offsets, sres, ws + scratch_at, nullptr, string_tokens, roads2);
+            launch_tape(doc, len, idx, n, max_depth, offsets, strs, sbuf2, tape2, tcap, ws + tape_at, nullptr, deep2);
+            hs2 = *sres;
+            ht2 = *reinterpret_cast<const tape_result_dev *>(ws + tape_at);
+            bool again = false;
+            if (roads2 == STRINGS_STREAM_ONLY && hs2.path == 2 && !hs2.overflow) { roads2 = STRINGS_WALK_ONLY; again = true; }
+            if (!deep2 && ht2.max_level >= TAPE_ONE_PASS_LEVELS) { deep2 = true; again = true; }
+            if (!again) { break; }
+          }
+          capacity_runs++;
+          deep_capacity_runs += deep2;
+          static const char *const legs[] = {"exact capacities", "a tape one word short", "a string buffer one byte short"};
+          for (size_t k = tcap; k < tape_cap; k++) {
+            if (tape2[k] != 0x5A5A5A5A5A5A5A5Aull) {
+              fprintf(stderr, "MISMATCH: overrun (%s): tape word %zu = %016llx was written, tape_cap = %zu (document %lu, %u bytes, road %u, deep %d)\n", legs[leg], k,
+                      (unsigned long long)tape2[k], tcap, docs, len, hs2.path, int(deep2));
+              return 1;
+            }
+          }
+          for (size_t k = scap; k < str_cap; k++) {
+            if (sbuf2[k] != 0x5A) {
+              fprintf(stderr, "MISMATCH: overrun (%s): string buffer byte %zu = %02x was written, string_buf_bytes = %zu (document %lu, %u bytes, road %u)\n", legs[leg], k, sbuf2[k],
+                      scap, docs, len, hs2.path);
+              return 1;
+            }
+          }
+          const bool clean = ht2.error_key == ~uint64_t(0) && hs2.first_bad == 0xFFFFFFFFu;
+          if (leg == 0) {
+            if (!clean || hs2.overflow || ht2.overflow || ht2.tape_words != tw || hs2.bytes != sb || memcmp(tape2, want.data(), tw * 8) != 0 || memcmp(sbuf2, want_s.data(), sb) != 0) {
+              fprintf(stderr, "MISMATCH: %s (%llu words, %llu bytes): overflow %u / %u, %llu words, %llu bytes, error key %llx (document %lu, %u bytes, road %u)\n", legs[leg],
+                      (unsigned long long)tw, (unsigned long long)sb, ht2.overflow, hs2.overflow, (unsigned long long)ht2.tape_words, (unsigned long long)hs2.bytes,
+                      (unsigned long long)ht2.error_key, docs, len, hs2.path);
+              return 1;
+            }
+          } else if (!clean || !(leg == 1 ? ht2.overflow : hs2.overflow)) { // what sjgpu_stage2_device turns into SJGPU_E_OVERFLOW
+            fprintf(stderr, "MISMATCH: %s and no overflow reported (tape %u, strings %u, error key %llx; document %lu, %u bytes, road %u)\n", legs[leg], ht2.overflow, hs2.overflow,
+                    (unsigned long long)ht2.error_key, docs, len, hs2.path);
+            return 1;
+          }
+        }
       }
     }
   }
   printf("%lu documents, %lu valid, 0 mismatches;", docs, valid);
   for (int k = 0; k < 32; k++) { if (codes[k]) { printf(" code %d: %lu", k, codes[k]); } }
-  printf(" (string roads: stream %lu, per-string %lu; second rounds: %lu)\n", roads[1], roads[2], reruns);
+  printf(" (string roads: stream %lu, per-string %lu; second rounds: %lu)", roads[1], roads[2], reruns);
+  printf(" [capacity runs: %lu, deep %lu]\n", capacity_runs, deep_capacity_runs);
   return 0;
 }

@@ -44,6 +44,47 @@ def test_kernel_sources_against_the_oracle(emu, seed, docs, max_kib):
     assert f"{docs} documents" in p.stdout.decode() and " 0 mismatches" in p.stdout.decode()
 
 
+@pytest.mark.parametrize("seed,docs,max_kib", [(1, 150, 200), (2026, 150, 200), (7, 10, 2500)])
+def test_exact_capacity_and_poisoned_guards(emu, seed, docs, max_kib):
+    """The contract is idx_words >= n + 3, tok_bytes >= idx_words, dst of len bytes -- and the write-outs are 16-byte vector stores with scalar heads and tails.
+    Mode `exact`: every launcher of `all` with idx_words = n + 3 (n from the oracle; len + 3 for a document that raises SJGPU_F_UNESCAPED_CTRL, whose n nobody
+    compares), every output array poisoned in front of the launch and the poison checked behind n + 3 words, n + 3 token bytes and out_len bytes (len when
+    the string is unclosed) -- twice, with two different patterns in the bytes behind in + len.  Its first document lies above 1 MiB: the range leg runs."""
+    import re
+    p = subprocess.run([emu, str(seed), str(docs), str(max_kib), "exact"], capture_output=True, timeout=1800)
+    out = p.stdout.decode()
+    assert p.returncode == 0, (out[-500:], p.stderr.decode()[-3000:])
+    assert f"{docs} documents" in out and " 0 mismatches" in out
+    m = re.search(r"exact: (\d+) documents at idx_words = n \+ 3, (\d+) range legs, (\d+) guards checked", out)
+    assert m and int(m.group(1)) >= docs // 2 and int(m.group(2)) >= 4 and int(m.group(3)) >= 20 * docs, out[-300:]
+
+
+@pytest.mark.parametrize("seed", [1, 2026])
+def test_a_list_that_does_not_fit(emu, seed):
+    """Mode `short`: idx_words = n + 2, n, n - 1, (n / 2) | 1 and 1 -- every stage-1 launcher takes its SJGPU_F_IDX_OVERFLOW branch: the flag is set, result.n is the
+    FULL count (a caller sizes its retry from it), nothing is stored at or behind the capacity, and in front of it a word is the oracle's or was never written."""
+    import re
+    p = subprocess.run([emu, str(seed), "150", "200", "short"], capture_output=True, timeout=1800)
+    out = p.stdout.decode()
+    assert p.returncode == 0, (out[-500:], p.stderr.decode()[-3000:])
+    assert "150 documents" in out and " 0 mismatches" in out
+    m = re.search(r"short: (\d+) documents at five capacities below n \+ 3, (\d+) range legs, (\d+) guards checked", out)
+    assert m and int(m.group(1)) >= 75 and int(m.group(2)) >= 10 and int(m.group(3)) >= 40 * int(m.group(1)), out[-300:]
+
+
+def test_the_guards_catch_a_tail_that_leaves_as_a_whole_vector(tmp_path):
+    """... and the guards have teeth: with SJGPU_SELFTEST_WIDE_TAIL the tail of every write-out of sjgpu_device.h (emit_indices, emit_span, emit_bytes) leaves as
+    one whole 16-byte vector instead of scalar stores -- up to three words, fifteen bytes too many.  The exact-capacity run must fail: with an overrun behind out_len on
+    every minify road, and with broken lists on the stage-1 roads."""
+    exe = _build(tmp_path, ("-DSJGPU_SELFTEST_WIDE_TAIL",))
+    p = subprocess.run([exe, "1", "40", "200", "exact"], capture_output=True, timeout=1800, env=dict(os.environ, SJ_EMU_MAX_FAILURES="100000"))
+    err = p.stderr.decode()
+    assert p.returncode != 0 and all(f"MISMATCH {road}: " in err and f"{road}: len " in err for road in ("split minify", "fused minify (16 KiB tiles)", "on-chip minify")), err[-3000:]
+    assert "overrun: out[" in err, err[-3000:]  # fifteen bytes behind out_len
+    # (a list's last vector ends inside its own three sentinels: there the wide tail shows as words of one wave overwritten by its neighbour's tail)
+    assert any(f"MISMATCH {road}: " in err for road in ("split stage 1", "fused stage 1 (16 KiB tiles)", "pipelined stage 1", "direct stage 1")), err[-3000:]
+
+
 @pytest.mark.parametrize("waves", ["4", "16"])
 def test_the_other_workgroup_shapes_of_the_single_pass_kernels(emu, waves):
     """The single-pass kernels run with eight waves per workgroup since round 4 (128 KiB / 64 KiB tiles: half the tickets and look-backs per byte); the

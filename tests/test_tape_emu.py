@@ -61,6 +61,23 @@ def test_fixtures(emu):
     assert "2 documents, 2 valid" in emu(docs, force_walk=1)  # the per-string kernels write the same buffer
 
 
+def test_exact_capacities_and_one_short(emu):
+    """tape_cap_words and string_buf_bytes may be exact.  Every valid document of every test of this file runs three more times inside the program -- with the
+    tape words and string bytes the oracle delivered as capacities (SUCCESS, the identical result), with the tape one word short and with the string buffer one
+    byte short (overflow) -- and the 0x5A fill behind the capacity given must be intact each time.  Here: that those legs do run, on both string roads, with the
+    sort's second pass (documents nested 64 deep and more) and with numbers beyond 19 digits (k_tape_slow_numbers)."""
+    import re
+    rng = np.random.default_rng(21)
+    docs = [jsongen.random_document(rng) for _ in range(120)] + [_big(rng, 50, 400) for _ in range(3)]
+    docs += [b"[" * d + b'"s"' + b"]" * d for d in (63, 64, 65, 200)] + [b'{"a":[' * 100 + b'{"k":"v"}' + b"]}" * 100]
+    docs += [b"[12345678901234567890123.5, 18446744073709551615, 1" + b"0" * 200 + b"e-190, 0." + b"7" * 90 + b', "x"]', b"[1,2,3]"]
+    for force_walk, road in ((0, "stream"), (1, "per-string")):
+        out = emu(docs, force_walk=force_walk)
+        assert f"{len(docs)} documents, {len(docs)} valid" in out and f"{road} {len(docs)}" in out, out
+        m = re.search(r"capacity runs: (\d+), deep (\d+)", out)
+        assert m and int(m.group(1)) >= 2 * len(docs) + 20 and int(m.group(2)) >= 6, out  # (a document without strings has two legs, the others three)
+
+
 def test_small_documents_valid_and_broken(emu):
     rng = np.random.default_rng(11)
     assert "400 documents, 400 valid" in emu([jsongen.random_document(rng) for _ in range(400)])
