@@ -1,6 +1,6 @@
 """In-tree native builds (explicit compiler invocations; outputs under simdjson_amd/lib/, build/ and oracle/_ref/).
 
-    libsjgpu.so            hipcc --offload-arch=gfx950   HIP kernels + C-ABI (include/sjgpu.h)   [product]
+    libsjgpu.so            hipcc --offload-arch=gfx950   HIP kernels + C-ABI (include/sjgpu*.h)   [product]
     libsjcorpus.so         gcc                           synthetic corpora                         [tooling]
     oracle/_ref/libsimdjson_mi355x.so  g++ against the reference's public headers: the simdjson::implementation
                            plug-in shim.  Needs the reference at BUILD time only.
@@ -52,16 +52,17 @@ def build_corpus(force=False):
     return _paths.LIB_CORPUS
 
 
-SJGPU_SOURCES = ("sjgpu_kernels.hip", "sjgpu_fused.hip", "sjgpu_small.hip", "sjgpu_finish.hip", "sjgpu_strings.hip", "sjgpu_string_stream.hip", "sjgpu_tape.hip", "sjgpu_tape_many.hip",
+SJGPU_SOURCES = ("sjgpu_kernels.hip", "sjgpu_fused.hip", "sjgpu_small.hip", "sjgpu_finish.hip", "sjgpu_strings.hip", "sjgpu_string_stream.hip", "sjgpu_tape.hip", "sjgpu_tape_many.hip", "sjgpu_query.hip",
                  "sjgpu_mgpu.hip", "sjgpu_comm.hip", "sjgpu_capi.hip", "sjgpu_capi_host.hip", "sjgpu_capi_stage2.hip", "stage1_finish.cpp")
-SJGPU_HEADERS = ("sj_block.h", "sj_number.h", "sj_tape_rules.h", "sj_string_stream.h", "sj_xcarry.h", "sj_pow5_table.inc", "sjgpu_internal.h", "sjgpu_device.h", "sjgpu_ctx.h")
+SJGPU_HEADERS = ("sj_block.h", "sj_number.h", "sj_tape_rules.h", "sj_string_stream.h", "sj_xcarry.h", "sj_pow5_table.inc", "sj_query_program.h", "sjgpu_internal.h", "sjgpu_device.h", "sjgpu_ctx.h")
 
 
 def sjgpu_source_stamp():
     """sha256 over everything libsjgpu.so is compiled from (names and bytes): what build/tests/STAMP.json records under "libsjgpu.so" when the
     library is built, and what the tests compare with -- a prebuilt library that travelled with OTHER sources is found out by content, not by mtime."""
     h = hashlib.sha256()
-    for f in [*_csrc(*SJGPU_SOURCES), *_csrc(*SJGPU_HEADERS), os.path.join(_paths.INCLUDE_DIR, "sjgpu.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_stream.h")]:
+    for f in [*_csrc(*SJGPU_SOURCES), *_csrc(*SJGPU_HEADERS), os.path.join(_paths.INCLUDE_DIR, "sjgpu.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_stream.h"),
+              os.path.join(_paths.INCLUDE_DIR, "sjgpu_query.h")]:
         h.update(os.path.relpath(f, _paths.REPO_ROOT).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()

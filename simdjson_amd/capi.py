@@ -50,6 +50,12 @@ STREAM_EXPORTS = ["sjgpu_stage2_many_device", "sjgpu_parse_many"]
 DOC_SPAN = np.dtype([("first_token", np.uint32), ("byte_begin", np.uint32), ("tape_begin", np.uint32), ("string_begin", np.uint32)])
 
 
+# what include/sjgpu_query.h declares (queries over device tapes: JSON pointers -> typed columns, a string column -> offsets + characters)
+QUERY_EXPORTS = ["sjgpu_at_pointers_device", "sjgpu_gather_strings_device"]
+# simdjson::error_code values a cell of sjgpu_at_pointers_device can hold instead of a tape tag (include/simdjson/error.h)
+INCORRECT_TYPE, INDEX_OUT_OF_BOUNDS, NO_SUCH_FIELD, INVALID_JSON_POINTER = 17, 19, 20, 22
+
+
 class ScanResult(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
 
@@ -139,6 +145,10 @@ def load_library():
     L.sjgpu_stage2_many_device.argtypes = [vp, vp, sz, vp, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp, sz, vp, sz, vp, u32p, u64p, u64p]
     L.sjgpu_parse_many.restype = ctypes.c_int
     L.sjgpu_parse_many.argtypes = [vp, vp, sz, ctypes.c_uint32, vp, sz, vp, sz, vp, sz, u32p, u64p, u64p]
+    L.sjgpu_at_pointers_device.restype = ctypes.c_int
+    L.sjgpu_at_pointers_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
+    L.sjgpu_gather_strings_device.restype = ctypes.c_int
+    L.sjgpu_gather_strings_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int
@@ -467,6 +477,61 @@ class DomParserImplementation:
         views = [(tape[int(table["tape_begin"][k]): int(table["tape_begin"][k + 1])], sbuf[int(table["string_begin"][k]): int(table["string_begin"][k + 1])])
                  for k in range(d)]
         return rc, d, views, (tape[: tw.value], sbuf[: sb.value], table)
+
+    def at_pointers_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, pointers, value_ptr, tag_ptr, stream=0):
+        """sjgpu_at_pointers_device: pointers = list of bytes (JSON pointers); value_ptr -> len(pointers) * docs uint64, tag_ptr -> as many bytes, row k = pointer k.
+        Only enqueues the walk.  -> 0 or a negative SJGPU_E_* for arguments the call refuses (raises on HIP errors)"""
+        blob = b"".join(pointers)
+        lens = np.array([len(x) for x in pointers], dtype=np.uint32)
+        rc = self.L.sjgpu_at_pointers_device(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs),
+                                             ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(pointers), value_ptr, tag_ptr,
+                                             stream or None)
+        if rc in (-2, -3):
+            raise SjgpuError(f"sjgpu_at_pointers_device error {rc}: {self.last_error()}")
+        return rc
+
+    def gather_strings_device(self, strbuf_ptr, strbuf_bytes, value_row_ptr, tag_row_ptr, docs, offsets_ptr, chars_ptr, chars_cap, stream=0):
+        """sjgpu_gather_strings_device: one column -> offsets_ptr (docs + 1 uint32) + chars_ptr (chars_cap bytes).  -> (code, bytes the characters take)"""
+        total = ctypes.c_uint64(0)
+        rc = self.L.sjgpu_gather_strings_device(self.h, strbuf_ptr, int(strbuf_bytes), value_row_ptr, tag_row_ptr, int(docs), offsets_ptr, chars_ptr or None, int(chars_cap),
+                                                stream or None, ctypes.byref(total))
+        if rc in (-2, -3):
+            raise SjgpuError(f"sjgpu_gather_strings_device error {rc}: {self.last_error()}")
+        return rc, int(total.value)
+
+    def extract_many(self, data, pointers, max_depth=1024):
+        """Field X of every record as a column: upload, stage 1, sjgpu_stage2_many_device and sjgpu_at_pointers_device with everything resident; only the columns come back.
+        -> (error_code of the first broken document or 0, documents delivered, tags uint8[K, docs], values uint64[K, docs])"""
+        import torch
+        a = _as_u8(data)
+        K = len(pointers)
+        empty = (np.zeros((K, 0), np.uint8), np.zeros((K, 0), np.uint64))
+        if len(a) == 0:
+            return (EMPTY, 0) + empty
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        buf = torch.from_numpy(np.concatenate([a, np.zeros(16, np.uint8)])).to(dev)
+        idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
+        rc = self.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, stream)
+        n, flags, _ = self.result(stream)
+        e1 = stage1_error_from_flags(n, flags)
+        if rc or e1:
+            return (rc or e1, 0) + empty
+        tape_cap = min(4 * n, len(a) + 3 * n) + 8
+        tape = torch.empty(tape_cap, dtype=torch.int64, device=dev)
+        sbuf = torch.empty(5 * (len(a) // 3) + 256, dtype=torch.uint8, device=dev)
+        table = torch.empty((n + 1) * 4, dtype=torch.int32, device=dev)
+        code, docs, tw, sb = self.stage2_many_device(buf.data_ptr(), len(a), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf.numel(), table.data_ptr(), n + 1,
+                                                     max_depth, stream)
+        if docs == 0 or K == 0:
+            return (code, docs, np.zeros((K, docs), np.uint8), np.zeros((K, docs), np.uint64))
+        values = torch.empty((K, docs), dtype=torch.int64, device=dev)
+        tags = torch.empty((K, docs), dtype=torch.uint8, device=dev)
+        rc = self.at_pointers_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, pointers, values.data_ptr(), tags.data_ptr(), stream)
+        if rc:
+            raise SjgpuError(f"sjgpu_at_pointers_device refused its arguments ({rc})")
+        torch.cuda.current_stream(dev).synchronize()
+        return code, docs, tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
 
     def result(self, stream=0):  # waits for `stream`
         r = ScanResult()

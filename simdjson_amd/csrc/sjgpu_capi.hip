@@ -102,6 +102,9 @@ void really_destroy(sjgpu_ctx *ctx) {
   dev_free(ctx->d_tmp);
   dev_free(ctx->d_stage2);
   dev_free(ctx->d_doc);
+  if (ctx->ev_query) { (void)hipEventSynchronize(ctx->ev_query); (void)hipEventDestroy(ctx->ev_query); }
+  dev_free(ctx->d_query);
+  if (ctx->h_query) { (void)hipHostFree(ctx->h_query); }
   if (ctx->stream) { (void)hipStreamDestroy(ctx->stream); }
   delete ctx;
 }

@@ -1,7 +1,9 @@
-// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h and include/sjgpu_stream.h, what follows the structural list on the device: the strings of a document, On-Demand's raw
-// key comparison, stage 2 (the DOM tape of a document, the tapes of a document stream), sjgpu_parse and sjgpu_parse_many.  Shared with the other units: sjgpu_ctx.h.
+// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h and include/sjgpu_query.h, what follows the structural list on the device: the strings of a
+// document, On-Demand's raw key comparison, stage 2 (the DOM tape of a document, the tapes of a document stream), sjgpu_parse and sjgpu_parse_many, and the queries over the tapes
+// (JSON pointers -> typed columns, a string column -> offsets + characters).  Shared with the other units: sjgpu_ctx.h.
 #include "sjgpu_ctx.h"
-#include "sjgpu_stream.h"
+#include "sjgpu_query.h"
+#include "sj_query_program.h"
 
 extern "C" {
 
@@ -342,6 +344,75 @@ int sjgpu_parse(sjgpu_ctx *ctx, const uint8_t *buf, size_t len, uint32_t max_dep
   SJ_TRY(ctx, hipStreamSynchronize(s));
   if (tape_words_out) { *tape_words_out = tw; }
   if (string_bytes_out) { *string_bytes_out = sb; }
+  return 0;
+}
+
+// ---- queries over device tapes (sjgpu_query.hip) ---------------------------------------------------------------------------------------------
+int sjgpu_at_pointers_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                             uint32_t docs, const uint8_t *pointers, const uint32_t *pointer_lens, uint32_t K, void *value_dev, void *tag_dev, void *stream) {
+  if (!ctx || !tape_dev || !string_buf_dev || !docs_dev || !value_dev || !tag_dev || (K && (!pointers || !pointer_lens))) { return SJGPU_E_BADARG; }
+  if ((reinterpret_cast<uintptr_t>(tape_dev) & 7u) || (reinterpret_cast<uintptr_t>(value_dev) & 7u) || (reinterpret_cast<uintptr_t>(docs_dev) & 15u)) { return SJGPU_E_BADARG; }
+  if (tape_words > 0xFFFFFFFFull || string_bytes > 0xFFFFFFFFull || docs >= 0xFFFFFFF0u) { return SJGPU_E_BADARG; } // the table's words are 32 bits
+  query_program prog;
+  if (!compile_query_program(pointers, pointer_lens, K, &prog)) { return SJGPU_E_BADARG; }
+  if (K == 0 || docs == 0) { return 0; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  // the blocks are the context's: the walk of the previous call must have read its pointers before they are overwritten
+  if (ctx->query_in_flight) {
+    SJ_TRY(ctx, hipEventSynchronize(ctx->ev_query));
+    ctx->query_in_flight = false;
+  }
+  if (!ctx->ev_query) { SJ_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_query, hipEventDisableTiming)); }
+  const size_t block = 256 + prog.bytes.size(); // [0] the table check's word, [256] the program
+  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, block);
+  if (rc) { return rc; }
+  if (ctx->h_query_bytes < block) {
+    if (ctx->h_query) { (void)hipHostFree(ctx->h_query); ctx->h_query = nullptr; ctx->h_query_bytes = 0; }
+    SJ_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_query), block, hipHostMallocDefault));
+    ctx->h_query_bytes = block;
+  }
+  std::memset(ctx->h_query, 0, 256);
+  std::memcpy(ctx->h_query + 256, prog.bytes.data(), prog.bytes.size());
+  hipStream_t s = pick(ctx, stream);
+  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
+  SJ_TRY(ctx, hipMemcpyAsync(ctx->d_query, ctx->h_query, block, hipMemcpyHostToDevice, s));
+  launch_query_check_table(table, docs, tape_words, string_bytes, reinterpret_cast<uint32_t *>(ctx->d_query), s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint32_t *const bad = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192); // (the pinned block's last slot: the scan and stage 2 use [0, 192))
+  SJ_TRY(ctx, hipMemcpyAsync(bad, ctx->d_query, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  if (*bad) { return SJGPU_E_BADARG; }
+  launch_at_pointers(static_cast<const uint64_t *>(tape_dev), static_cast<const uint8_t *>(string_buf_dev), table, docs, ctx->d_query + 256, prog.tokens_at, prog.keys_at, K,
+                     static_cast<uint64_t *>(value_dev), static_cast<uint8_t *>(tag_dev), s);
+  SJ_TRY(ctx, hipGetLastError());
+  SJ_TRY(ctx, hipEventRecord(ctx->ev_query, s));
+  ctx->query_in_flight = true;
+  return 0;
+}
+
+int sjgpu_gather_strings_device(sjgpu_ctx *ctx, const void *string_buf_dev, uint64_t string_bytes, const void *value_row_dev, const void *tag_row_dev, uint32_t docs,
+                                void *offsets_dev, void *chars_dev, uint64_t chars_cap, void *stream, uint64_t *bytes_out) {
+  if (bytes_out) { *bytes_out = 0; }
+  if (!ctx || !string_buf_dev || !offsets_dev || (docs && (!value_row_dev || !tag_row_dev)) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
+  if ((reinterpret_cast<uintptr_t>(offsets_dev) & 3u) || (reinterpret_cast<uintptr_t>(value_row_dev) & 7u) || docs >= 0xFFFFFFF0u) { return SJGPU_E_BADARG; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_tmp(ctx, gather_workspace_bytes(docs));
+  if (rc) { return rc; }
+  hipStream_t s = pick(ctx, stream);
+  const uint64_t *value = static_cast<const uint64_t *>(value_row_dev);
+  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  const void *total_dev = launch_gather_offsets(value, static_cast<const uint8_t *>(tag_row_dev), docs, string_bytes, offsets, ctx->d_tmp, s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
+  SJ_TRY(ctx, hipMemcpyAsync(total, total_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  const uint64_t bytes = *total;
+  if (bytes_out) { *bytes_out = bytes; }
+  if (bytes > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
+  if (bytes > chars_cap) { return SJGPU_E_OVERFLOW; }
+  launch_gather_copy(static_cast<const uint8_t *>(string_buf_dev), value, offsets, docs, bytes, static_cast<uint8_t *>(chars_dev), s);
+  SJ_TRY(ctx, hipGetLastError());
+  SJ_TRY(ctx, hipStreamSynchronize(s));
   return 0;
 }
 

@@ -159,6 +159,12 @@ struct sjgpu_ctx {
   size_t d_stage2_bytes = 0;
   uint8_t *d_doc = nullptr; // [tape words][string buffer] of sjgpu_parse
   size_t d_doc_bytes = 0;
+  // sjgpu_at_pointers_device: the compiled pointers travel page-locked block -> device block -> the walk's LDS; [0] of the device block is the table check's word.
+  // ev_query is recorded behind the walk: the next call waits for it before it writes either block again
+  uint8_t *d_query = nullptr, *h_query = nullptr;
+  size_t d_query_bytes = 0, h_query_bytes = 0;
+  hipEvent_t ev_query = nullptr;
+  bool query_in_flight = false;
   // look-ahead over a registered stream (sjgpu_stream_register): the raw structurals of ONE span of the stream, in page-locked
   // host memory, from which the windows document_stream asks for are cut without touching the GPU again
   struct span_slot {

@@ -283,6 +283,17 @@ void launch_many_ordinals(const uint32_t *idx, uint32_t n, const many_workspace 
 // (docs, total_words: what the host read back -- the table has docs + 1 entries, nothing is written at or beyond tape[total_words]; table: 16-byte aligned)
 void launch_many_relocate(const uint32_t *idx, uint32_t n, uint32_t docs, uint64_t total_words, const many_workspace &m, const tape_stream_view &v,
                           const strings_result_dev *sres, doc_span_dev *table, uint64_t *tape, hipStream_t s);
+// ---- queries over device tapes (sjgpu_query.hip: sjgpu_at_pointers_device, sjgpu_gather_strings_device) ------------------------------------------
+// *bad |= 1 (a device word the caller cleared) when the table's tape_begin / string_begin run backwards or its last entry lies beyond the arrays
+void launch_query_check_table(const doc_span_dev *table, uint32_t docs, uint64_t tape_words, uint64_t string_bytes, uint32_t *bad, hipStream_t s);
+// program: what compile_query_program (sj_query_program.h) left, in device memory, 16-byte aligned; K >= 1, docs >= 1; a table that passed the check
+void launch_at_pointers(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t tokens_at,
+                        uint32_t keys_at, uint32_t K, uint64_t *value, uint8_t *tag, hipStream_t s);
+// offsets[0 .. docs] = exclusive sum of the string cells' lengths; -> the device address of the 64-bit total (workspace: gather_workspace_bytes(docs), 256-byte aligned)
+size_t gather_workspace_bytes(uint32_t docs);
+const void *launch_gather_offsets(const uint64_t *value, const uint8_t *tag, uint32_t docs, uint64_t string_bytes, uint32_t *offsets, void *workspace, hipStream_t s);
+// total: what the host read back and found to fit chars
+void launch_gather_copy(const uint8_t *string_buf, const uint64_t *value, const uint32_t *offsets, uint32_t docs, uint64_t total, uint8_t *chars, hipStream_t s);
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);

@@ -1,0 +1,307 @@
+// simdjson_amd/csrc/sjgpu_query.hip -- queries over device tapes: a batched dom::element::at_pointer (sjgpu_at_pointers_device) and the
+// string column as offsets + characters (sjgpu_gather_strings_device).  Contract: include/sjgpu_query.h.
+//
+// The walk.  K pointers x docs documents = K * docs CELLS; one lane walks one cell, the lanes of a workgroup take consecutive documents of ONE
+// pointer: the column stores are coalesced, the workgroup's pointer -- its tokens as sj_query_program.h compiled them and its
+// unescaped key bytes, 2.3 KiB at most -- is copied to LDS once and read from there at every step, and the K lanes that walk one document
+// (in K workgroups) find the lines its first visitor brought in.  NDJSON records are tens to hundreds of tape words: a cooperative walk
+// per document would idle most of a wave.
+// What the reference does per step (dom/object-inl.h:104-147 + :246-254, dom/array-inl.h:94-121 + array::at, dom/element-inl.h:427-446)
+// is here a look at the tag of the word the walk stands on and one of three readings of the token, all prepared on the host:
+//   {   the token as a key: its code if the escape is invalid, else the first field whose key record has the token's length and bytes
+//   [   the token as an index: its code, else the element with that ordinal
+//   else (a scalar) the verdict on the rest of the pointer
+// Siblings are stepped over in O(1): a container word carries the index behind its partner in its low 32 bits, a number is two words, everything
+// else one.  The walk only ever looks at the tag of a word it ARRIVED at by such steps, so a number's value word is never taken for a tag.
+// Keys: the record is [u32 length][bytes][0] at any byte of the string buffer; the length is compared first and bytes are read only when it
+// agrees, eight at a time while eight remain and one by one behind them -- never a byte behind the key's own.
+// Nothing is trusted beyond the table check the host ran (the table ascends and ends inside the arrays): an index that leaves the document's
+// slice, a step that does not advance, a record that leaves the document's string slice end the walk as "not found" (20 / 19).
+//
+// The gather.  Lengths from the column straight into the caller's offsets array, the context's exclusive scan over it (enqueue_scan), a total
+// in 64 bits beside it (per-block sums, then one workgroup), and a copy that is parallel over the OUTPUT: a lane owns 16 bytes of it, finds the cell of its first byte by a search
+// in the offsets and follows the cells from there -- a string of 100 KiB is 6 400 lanes' work, not one lane's.
+#include "sjgpu_device.h"
+#include "sj_query_program.h"
+
+namespace sjgpu {
+namespace {
+
+constexpr u32 QUERY_THREADS = 256;
+constexpr u64 LOW32 = 0xFFFFFFFFull, PAYLOAD = 0x00FFFFFFFFFFFFFFull;
+
+typedef u32 __attribute__((aligned(1))) u32_unaligned;
+typedef u64 __attribute__((aligned(1))) u64_unaligned;
+
+__device__ __forceinline__ bool is_number_tag(u32 t) { return t == 'l' || t == 'u' || t == 'd'; }
+__device__ __forceinline__ bool is_container_tag(u32 t) { return t == '{' || t == '['; }
+
+// the index behind the element that begins at word i (whose word is w); base: the document's first word.  A step that would not advance
+// (a tape that is not one) returns `end`: the level is over.
+__device__ __forceinline__ u64 behind(u64 i, u64 w, u64 base, u64 end) {
+  const u32 t = u32(w >> 56);
+  const u64 next = is_container_tag(t) ? base + (w & LOW32) : i + (is_number_tag(t) ? 2u : 1u);
+  return next > i ? next : end;
+}
+
+__device__ __forceinline__ bool key_equals(const u8 *__restrict__ rec, const u8 *key /* LDS, 8-byte aligned */, u32 len) {
+  u32 j = 0;
+  for (; j + 8 <= len; j += 8) {
+    if (*reinterpret_cast<const u64_unaligned *>(rec + j) != *reinterpret_cast<const u64 *>(key + j)) { return false; }
+  }
+  for (; j < len; j++) {
+    if (rec[j] != key[j]) { return false; }
+  }
+  return true;
+}
+
+// grid: K rows of row_blocks workgroups, row k = pointer k (one dimension: at most 64 * 2^24 workgroups)
+__global__ __launch_bounds__(QUERY_THREADS) void k_at_pointers(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table, u32 docs,
+                                                             const u8 *__restrict__ prog, u32 tokens_at, u32 keys_at, u32 row_blocks, u64 *__restrict__ value, u8 *__restrict__ tag) {
+  __shared__ query_token s_tok[QUERY_MAX_TOKENS];
+  __shared__ u64 s_key[QUERY_KEY_AREA / 8];
+  const u32 k = blockIdx.x / row_blocks, row_block = blockIdx.x - k * row_blocks;
+  const query_pointer qp = reinterpret_cast<const query_pointer *>(prog)[k];
+  {
+    // the pointer's tokens (4 words of 8 bytes each) and its key area: what is behind the last key is never compared
+    const u64 *src = reinterpret_cast<const u64 *>(prog + tokens_at) + u64(qp.first_token) * (sizeof(query_token) / 8);
+    u64 *dst = reinterpret_cast<u64 *>(s_tok);
+    for (u32 j = threadIdx.x; j < qp.tokens * u32(sizeof(query_token) / 8); j += QUERY_THREADS) { dst[j] = src[j]; }
+    u32 key_words = 0;
+    if (qp.tokens) {
+      const query_token last = reinterpret_cast<const query_token *>(prog + tokens_at)[qp.first_token + qp.tokens - 1u];
+      key_words = (last.key_off + last.key_len + 7u) / 8u;
+    }
+    key_words = key_words < QUERY_KEY_AREA / 8 ? key_words : QUERY_KEY_AREA / 8;
+    const u64 *ksrc = reinterpret_cast<const u64 *>(prog + keys_at + qp.keys_at);
+    for (u32 j = threadIdx.x; j < key_words; j += QUERY_THREADS) { s_key[j] = ksrc[j]; }
+  }
+  lds_writes_done();
+  __syncthreads();
+  const u64 d64 = u64(row_block) * QUERY_THREADS + threadIdx.x;
+  if (d64 >= docs) { return; }
+  const u32 d = u32(d64);
+  const uint4 a = *reinterpret_cast<const uint4 *>(table + d), b = *reinterpret_cast<const uint4 *>(table + d + 1u);
+  const u64 base = a.z, doc_end = b.z; // the document's words: [base, doc_end)
+  const u64 str_base = a.w, str_end = b.w;
+  u32 code = qp.code;
+  u64 cur = base + 1u; // the root: behind the root word
+  u64 w = 0;
+  if (!code) {
+    if (cur < doc_end) { w = tape[cur]; } else { code = QUERY_NO_SUCH_FIELD; }
+  }
+  for (u32 t = 0; t < qp.tokens && !code; t++) {
+    const u32 kind = u32(w >> 56);
+    if (kind == '{') {
+      if (s_tok[t].key_code) { code = s_tok[t].key_code; break; }
+      const u32 klen = s_tok[t].key_len;
+      const u8 *key = reinterpret_cast<const u8 *>(s_key) + s_tok[t].key_off;
+      u64 end = base + (w & LOW32) - 1u; // the closing word
+      end = end < doc_end ? end : doc_end;
+      u64 i = cur + 1u;
+      bool found = false;
+      while (i + 1u < end) { // a key word and the first word of its value
+        const u64 kw = tape[i], vw = tape[i + 1u];
+        const u64 rec = str_base + (kw & PAYLOAD);
+        if (rec + 4u <= str_end) {
+          const u32 len = *reinterpret_cast<const u32_unaligned *>(sbuf + rec);
+          if (len == klen && rec + 4u + u64(len) <= str_end && key_equals(sbuf + rec + 4u, key, klen)) {
+            found = true;
+            cur = i + 1u;
+            w = vw;
+            break;
+          }
+        }
+        i = behind(i + 1u, vw, base, end);
+      }
+      if (!found) { code = QUERY_NO_SUCH_FIELD; }
+    } else if (kind == '[') {
+      if (s_tok[t].arr_code) { code = s_tok[t].arr_code; break; }
+      const u64 want = s_tok[t].arr_index;
+      u64 end = base + (w & LOW32) - 1u;
+      end = end < doc_end ? end : doc_end;
+      u64 i = cur + 1u, ordinal = 0;
+      bool found = false;
+      while (i < end) {
+        const u64 ew = tape[i];
+        if (ordinal == want) {
+          found = true;
+          cur = i;
+          w = ew;
+          break;
+        }
+        ordinal++;
+        i = behind(i, ew, base, end);
+      }
+      if (!found) { code = QUERY_INDEX_OUT_OF_BOUNDS; }
+    } else {
+      code = s_tok[t].scalar_code;
+    }
+  }
+  u32 out_tag = code;
+  u64 out_value = 0;
+  if (!code) {
+    const u32 kind = u32(w >> 56);
+    out_tag = kind;
+    if (is_number_tag(kind)) {
+      out_value = cur + 1u < doc_end ? tape[cur + 1u] : 0;
+    } else if (kind == 't') {
+      out_value = 1;
+    } else if (kind == '"') {
+      const u64 rec = str_base + (w & PAYLOAD);
+      const u32 len = rec + 4u <= str_end ? *reinterpret_cast<const u32_unaligned *>(sbuf + rec) : 0u;
+      out_value = (u64(len) << 32) | ((rec + 4u) & LOW32);
+    } else if (is_container_tag(kind)) {
+      out_value = ((base + (w & LOW32)) << 32) | cur;
+    }
+  }
+  const u64 cell = u64(k) * docs + d;
+  tag[cell] = u8(out_tag);
+  value[cell] = out_value;
+}
+
+// one thread per entry: does the table ascend and end inside the arrays?  (A table of docs + 1 entries costs a fraction of the walk it guards.)
+__global__ __launch_bounds__(QUERY_THREADS) void k_query_check_table(const doc_span_dev *__restrict__ table, u32 docs, u64 tape_words, u64 string_bytes, u32 *__restrict__ bad) {
+  const u64 d64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (d64 > docs) { return; }
+  const u32 d = u32(d64);
+  const uint4 a = *reinterpret_cast<const uint4 *>(table + d);
+  bool wrong;
+  if (d == docs) {
+    wrong = a.z > tape_words || a.w > string_bytes;
+  } else {
+    const uint4 b = *reinterpret_cast<const uint4 *>(table + d + 1u);
+    wrong = a.z > b.z || a.w > b.w;
+  }
+  if (wrong) { atomicOr(bad, 1u); }
+}
+
+// ---- the gather -------------------------------------------------------------------------------------------------------------------------------
+struct gather_ctrl {
+  u64 total;     // the sum of the lengths in 64 bits (the scan's words wrap at 2^32)
+  u32 n_plus_1;  // docs + 1: the length of the scan
+  u32 pad;
+};
+
+constexpr u32 GATHER_PER_THREAD = 8, GATHER_BLOCK = QUERY_THREADS * GATHER_PER_THREAD;
+// offsets[d] = the length of cell d (a string inside the buffer) or 0; offsets[docs] = 0: the exclusive scan in place makes them the offsets.
+// block_sums[block]: the lengths of the block's 2 048 cells in 64 bits (one atomic per wave on ONE word was 165 us for 862 116 cells)
+__global__ __launch_bounds__(QUERY_THREADS) void k_gather_lengths(const u64 *__restrict__ value, const u8 *__restrict__ tag, u32 docs, u64 string_bytes,
+                                                                u32 *__restrict__ offsets, u64 *__restrict__ block_sums) {
+  __shared__ u64 s_sum[QUERY_THREADS / 64];
+  const u64 first = u64(blockIdx.x) * GATHER_BLOCK + threadIdx.x;
+  u64 sum = 0;
+#pragma unroll
+  for (u32 j = 0; j < GATHER_PER_THREAD; j++) {
+    const u64 d64 = first + u64(j) * QUERY_THREADS;
+    u32 len = 0;
+    if (d64 < docs && tag[d64] == '"') {
+      const u64 v = value[d64];
+      const u64 at = v & LOW32, l = v >> 32;
+      len = at + l <= string_bytes ? u32(l) : 0u;
+    }
+    if (d64 <= docs) { offsets[d64] = len; }
+    sum += len;
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); }
+  if (lane_id() == 0) { s_sum[threadIdx.x >> 6] = sum; }
+  lds_writes_done();
+  __syncthreads();
+  if (threadIdx.x == 0) { block_sums[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]; }
+}
+
+// one workgroup: the total, and the length of the scan
+__global__ __launch_bounds__(QUERY_THREADS) void k_gather_total(const u64 *__restrict__ block_sums, u32 blocks, u32 docs, gather_ctrl *__restrict__ ctrl) {
+  __shared__ u64 s_sum[QUERY_THREADS / 64];
+  u64 sum = 0;
+  for (u32 j = threadIdx.x; j < blocks; j += QUERY_THREADS) { sum += block_sums[j]; }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); }
+  if (lane_id() == 0) { s_sum[threadIdx.x >> 6] = sum; }
+  lds_writes_done();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    ctrl->total = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    ctrl->n_plus_1 = docs + 1u;
+    ctrl->pad = 0;
+  }
+}
+
+constexpr u32 GATHER_CHUNK = 16;
+// a lane: 16 bytes of the output, [chunk * 16, ...) of `total`
+__global__ __launch_bounds__(QUERY_THREADS) void k_gather_copy(const u8 *__restrict__ sbuf, const u64 *__restrict__ value, const u32 *__restrict__ offsets, u32 docs, u64 total,
+                                                             u8 *__restrict__ chars) {
+  const u64 first = (u64(blockIdx.x) * QUERY_THREADS + threadIdx.x) * GATHER_CHUNK;
+  if (first >= total) { return; }
+  const u32 count = total - first < GATHER_CHUNK ? u32(total - first) : GATHER_CHUNK;
+  // the cell of byte `first`: the LAST d with offsets[d] <= first (cells of no bytes in front of it share its offset and are passed over)
+  u32 lo = 0, hi = docs; // offsets[0] = 0 <= first < total = offsets[docs]
+  while (hi - lo > 1u) {
+    const u32 mid = lo + (hi - lo) / 2u;
+    if (offsets[mid] <= first) { lo = mid; } else { hi = mid; }
+  }
+  u32 d = lo;
+  u64 cell_begin = offsets[d], cell_end = offsets[d + 1u];
+  const u8 *src = sbuf + (value[d] & LOW32);
+  u32 bytes[GATHER_CHUNK / 4] = {0, 0, 0, 0};
+#pragma unroll
+  for (u32 j = 0; j < GATHER_CHUNK; j++) {
+    if (j < count) {
+      const u64 pos = first + j;
+      while (pos >= cell_end && d + 1u < docs) { // (total = offsets[docs] > pos: a cell with bytes lies ahead)
+        d++;
+        cell_begin = cell_end;
+        cell_end = offsets[d + 1u];
+        src = sbuf + (value[d] & LOW32);
+      }
+      bytes[j / 4] |= u32(src[pos - cell_begin]) << (8u * (j & 3u));
+    }
+  }
+  u8 *dst = chars + first;
+  if (count == GATHER_CHUNK && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+    *reinterpret_cast<uint4 *>(dst) = make_uint4(bytes[0], bytes[1], bytes[2], bytes[3]);
+  } else {
+#pragma unroll
+    for (u32 j = 0; j < GATHER_CHUNK; j++) {
+      if (j < count) { dst[j] = u8(bytes[j / 4] >> (8u * (j & 3u))); }
+    }
+  }
+}
+
+static inline u32 blocks_of(u64 n, u32 per) { return u32((n + per - 1) / per); }
+
+} // namespace
+
+void launch_query_check_table(const doc_span_dev *table, uint32_t docs, uint64_t tape_words, uint64_t string_bytes, uint32_t *bad, hipStream_t s) {
+  hipLaunchKernelGGL(k_query_check_table, dim3(blocks_of(u64(docs) + 1, QUERY_THREADS)), dim3(QUERY_THREADS), 0, s, table, docs, tape_words, string_bytes, bad);
+}
+
+void launch_at_pointers(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t tokens_at,
+                        uint32_t keys_at, uint32_t K, uint64_t *value, uint8_t *tag, hipStream_t s) {
+  const u32 row_blocks = blocks_of(docs, QUERY_THREADS);
+  hipLaunchKernelGGL(k_at_pointers, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, docs, program, tokens_at, keys_at, row_blocks, value, tag);
+}
+
+// [ctrl, 256 bytes][the blocks' sums][the scan's block sums]
+static inline size_t gather_sums_bytes(uint32_t docs) { return (size_t(blocks_of(u64(docs) + 1, GATHER_BLOCK)) * sizeof(u64) + 255) & ~size_t(255); }
+size_t gather_workspace_bytes(uint32_t docs) { return 256 + gather_sums_bytes(docs) + (size_t(blocks_of(u64(docs) + 1, 4096)) + 64) * sizeof(int); }
+
+const void *launch_gather_offsets(const uint64_t *value, const uint8_t *tag, uint32_t docs, uint64_t string_bytes, uint32_t *offsets, void *workspace, hipStream_t s) {
+  uint8_t *ws = static_cast<uint8_t *>(workspace);
+  gather_ctrl *ctrl = reinterpret_cast<gather_ctrl *>(ws);
+  u64 *block_sums = reinterpret_cast<u64 *>(ws + 256);
+  int *partial = reinterpret_cast<int *>(ws + 256 + gather_sums_bytes(docs));
+  const u32 blocks = blocks_of(u64(docs) + 1, GATHER_BLOCK);
+  hipLaunchKernelGGL(k_gather_lengths, dim3(blocks), dim3(QUERY_THREADS), 0, s, value, tag, docs, string_bytes, offsets, block_sums);
+  hipLaunchKernelGGL(k_gather_total, dim3(1), dim3(QUERY_THREADS), 0, s, block_sums, blocks, docs, ctrl);
+  enqueue_scan(reinterpret_cast<int *>(offsets), docs + 1u, &ctrl->n_plus_1, partial, s);
+  return ctrl;
+}
+
+void launch_gather_copy(const uint8_t *string_buf, const uint64_t *value, const uint32_t *offsets, uint32_t docs, uint64_t total, uint8_t *chars, hipStream_t s) {
+  if (total == 0 || docs == 0) { return; }
+  hipLaunchKernelGGL(k_gather_copy, dim3(blocks_of(total, QUERY_THREADS * GATHER_CHUNK)), dim3(QUERY_THREADS), 0, s, string_buf, value, offsets, docs, total, chars);
+}
+
+} // namespace sjgpu
