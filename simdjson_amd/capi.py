@@ -56,6 +56,10 @@ QUERY_EXPORTS = ["sjgpu_at_pointers_device", "sjgpu_gather_strings_device"]
 INCORRECT_TYPE, INDEX_OUT_OF_BOUNDS, NO_SUCH_FIELD, INVALID_JSON_POINTER = 17, 19, 20, 22
 
 
+# what include/sjgpu_paths.h declares (JSONPath with wildcards over device tapes: one ragged column, CSR style)
+PATH_EXPORTS = ["sjgpu_at_paths_device"]
+
+
 class ScanResult(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
 
@@ -149,6 +153,8 @@ def load_library():
     L.sjgpu_at_pointers_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
     L.sjgpu_gather_strings_device.restype = ctypes.c_int
     L.sjgpu_gather_strings_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, u64p]
+    L.sjgpu_at_paths_device.restype = ctypes.c_int
+    L.sjgpu_at_paths_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int
@@ -532,6 +538,65 @@ class DomParserImplementation:
             raise SjgpuError(f"sjgpu_at_pointers_device refused its arguments ({rc})")
         torch.cuda.current_stream(dev).synchronize()
         return code, docs, tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
+
+    def at_paths_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap, stream=0):
+        """sjgpu_at_paths_device: paths = list of bytes (JSONPath, wildcards allowed); offsets_ptr -> len(paths) * docs + 1 uint32, status_ptr -> len(paths) * docs bytes,
+        value_ptr / tag_ptr -> match_cap uint64 / bytes.  -> (code, matches): 0, CAPACITY or a negative SJGPU_E_* (raises on HIP errors)"""
+        blob = b"".join(paths)
+        lens = np.array([len(x) for x in paths], dtype=np.uint32)
+        matches = ctypes.c_uint64(0)
+        rc = self.L.sjgpu_at_paths_device(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs),
+                                          ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(paths), offsets_ptr, status_ptr or None,
+                                          value_ptr or None, tag_ptr or None, int(match_cap), stream or None, ctypes.byref(matches))
+        if rc in (-2, -3):
+            raise SjgpuError(f"sjgpu_at_paths_device error {rc}: {self.last_error()}")
+        return rc, int(matches.value)
+
+    def explode_many(self, data, paths, max_depth=1024, first_cap=None):
+        """The arrays of every record as one ragged column: upload, stage 1, sjgpu_stage2_many_device and sjgpu_at_paths_device with everything resident (the twin of
+        extract_many).  At most two calls of sjgpu_at_paths_device: a second one with the capacity the first reported (first_cap: the first call's guess, by default one
+        match per tape word in eight).
+        -> (error_code of the first broken document or 0, documents delivered, status uint8[K, docs], offsets uint32[K * docs + 1], tags uint8[matches], values uint64[matches])"""
+        import torch
+        a = _as_u8(data)
+        K = len(paths)
+
+        def nothing(code, docs):
+            return code, docs, np.zeros((K, docs), np.uint8), np.zeros(K * docs + 1, np.uint32), np.zeros(0, np.uint8), np.zeros(0, np.uint64)
+        if len(a) == 0:
+            return nothing(EMPTY, 0)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        buf = torch.from_numpy(np.concatenate([a, np.zeros(16, np.uint8)])).to(dev)
+        idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
+        rc = self.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, stream)
+        n, flags, _ = self.result(stream)
+        e1 = stage1_error_from_flags(n, flags)
+        if rc or e1:
+            return nothing(rc or e1, 0)
+        tape_cap = min(4 * n, len(a) + 3 * n) + 8
+        tape = torch.empty(tape_cap, dtype=torch.int64, device=dev)
+        sbuf = torch.empty(5 * (len(a) // 3) + 256, dtype=torch.uint8, device=dev)
+        table = torch.empty((n + 1) * 4, dtype=torch.int32, device=dev)
+        code, docs, tw, sb = self.stage2_many_device(buf.data_ptr(), len(a), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf.numel(), table.data_ptr(), n + 1,
+                                                     max_depth, stream)
+        if docs == 0 or K == 0:
+            return nothing(code, docs)
+        offsets = torch.empty(K * docs + 1, dtype=torch.int32, device=dev)
+        status = torch.empty((K, docs), dtype=torch.uint8, device=dev)
+        cap = int(tw // 8 + 1 if first_cap is None else first_cap)
+        for attempt in range(2):
+            values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            rc, matches = self.at_paths_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, paths, offsets.data_ptr(), status.data_ptr(), values.data_ptr(),
+                                               tags.data_ptr(), cap, stream)
+            if rc != -5:  # SJGPU_E_OVERFLOW: once more, with what it asks for
+                break
+            cap = matches
+        if rc:
+            raise SjgpuError(f"sjgpu_at_paths_device refused its arguments ({rc})")
+        torch.cuda.current_stream(dev).synchronize()
+        return code, docs, status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(), values[:matches].cpu().numpy().view(np.uint64)
 
     def result(self, stream=0):  # waits for `stream`
         r = ScanResult()

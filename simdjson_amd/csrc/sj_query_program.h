@@ -44,6 +44,58 @@ struct query_program {
   uint32_t tokens_at = 0, keys_at = 0;
 };
 
+// the tokens of ONE pointer p[0 .. L) that begins with a slash, appended to toks and to keys (keys_base: where this pointer's key area begins in keys; key_off
+// is counted from there).  *count: the tokens this key area holds so far; -> false: more than `room` of them.  Shared with sj_path_program.h.
+inline bool append_pointer_tokens(const uint8_t *p, uint32_t L, uint32_t keys_base, uint32_t room, std::vector<query_token> *toks, std::vector<uint8_t> *keys_out, uint32_t *count) {
+  std::vector<uint8_t> &keys = *keys_out;
+  uint32_t slash = 0;
+  while (slash < L) {
+    uint32_t end = slash + 1;
+    while (end < L && p[end] != '/') { end++; }
+    if (*count == room) { return false; }
+    const uint8_t *t = p + slash + 1;
+    const uint32_t tl = end - slash - 1;
+    query_token q;
+    memset(&q, 0, sizeof q);
+    // as a key
+    q.key_off = uint32_t(keys.size()) - keys_base;
+    for (uint32_t j = 0; j < tl; j++) {
+      if (t[j] != '~') { keys.push_back(t[j]); continue; }
+      const uint8_t next = j + 1 < tl ? t[j + 1] : 0; // (the reference reads the terminator behind its copy of the token)
+      if (next == '0') { keys.push_back('~'); j++; }
+      else if (next == '1') { keys.push_back('/'); j++; }
+      else { q.key_code = QUERY_INVALID_JSON_POINTER; break; }
+    }
+    q.key_len = uint32_t(keys.size()) - keys_base - q.key_off;
+    while (keys.size() & 7u) { keys.push_back(0); }
+    // as an index
+    if (tl == 1 && t[0] == '-' && end == L) { q.arr_code = QUERY_INDEX_OUT_OF_BOUNDS; }
+    else {
+      uint64_t index = 0;
+      for (uint32_t j = 0; j < tl && !q.arr_code; j++) {
+        const uint8_t digit = uint8_t(t[j] - '0');
+        if (digit > 9) { q.arr_code = QUERY_INCORRECT_TYPE; }
+        else if (j > 0 && t[0] == '0') { q.arr_code = QUERY_INVALID_JSON_POINTER; }
+        else if (index > (~uint64_t(0) - digit) / 10) { q.arr_code = QUERY_INDEX_OUT_OF_BOUNDS; }
+        else { index = index * 10 + digit; }
+      }
+      if (tl == 0) { q.arr_code = QUERY_INVALID_JSON_POINTER; }
+      q.arr_index = q.arr_code ? 0 : index;
+    }
+    // by a scalar: the rest from this token's slash on
+    q.scalar_code = QUERY_NO_SUCH_FIELD;
+    for (uint32_t j = slash; j < L; j++) {
+      if (p[j] != '~') { continue; }
+      if (j + 1 == L || (p[j + 1] != '0' && p[j + 1] != '1')) { q.scalar_code = QUERY_INVALID_JSON_POINTER; }
+      break;
+    }
+    toks->push_back(q);
+    (*count)++;
+    slash = end;
+  }
+  return true;
+}
+
 // -> false: K, a length or a token count beyond the limits
 inline bool compile_query_program(const uint8_t *pointers, const uint32_t *lens, uint32_t K, query_program *out) {
   if (K > QUERY_MAX_POINTERS) { return false; }
@@ -63,51 +115,7 @@ inline bool compile_query_program(const uint8_t *pointers, const uint32_t *lens,
     qp.keys_at = uint32_t(keys.size());
     if (L == 0) { continue; }
     if (p[0] != '/') { qp.code = QUERY_INVALID_JSON_POINTER; continue; }
-    uint32_t slash = 0;
-    while (slash < L) {
-      uint32_t end = slash + 1;
-      while (end < L && p[end] != '/') { end++; }
-      if (qp.tokens == QUERY_MAX_TOKENS) { return false; }
-      const uint8_t *t = p + slash + 1;
-      const uint32_t tl = end - slash - 1;
-      query_token q;
-      memset(&q, 0, sizeof q);
-      // as a key
-      q.key_off = uint32_t(keys.size()) - qp.keys_at;
-      for (uint32_t j = 0; j < tl; j++) {
-        if (t[j] != '~') { keys.push_back(t[j]); continue; }
-        const uint8_t next = j + 1 < tl ? t[j + 1] : 0; // (the reference reads the terminator behind its copy of the token)
-        if (next == '0') { keys.push_back('~'); j++; }
-        else if (next == '1') { keys.push_back('/'); j++; }
-        else { q.key_code = QUERY_INVALID_JSON_POINTER; break; }
-      }
-      q.key_len = uint32_t(keys.size()) - qp.keys_at - q.key_off;
-      while (keys.size() & 7u) { keys.push_back(0); }
-      // as an index
-      if (tl == 1 && t[0] == '-' && end == L) { q.arr_code = QUERY_INDEX_OUT_OF_BOUNDS; }
-      else {
-        uint64_t index = 0;
-        for (uint32_t j = 0; j < tl && !q.arr_code; j++) {
-          const uint8_t digit = uint8_t(t[j] - '0');
-          if (digit > 9) { q.arr_code = QUERY_INCORRECT_TYPE; }
-          else if (j > 0 && t[0] == '0') { q.arr_code = QUERY_INVALID_JSON_POINTER; }
-          else if (index > (~uint64_t(0) - digit) / 10) { q.arr_code = QUERY_INDEX_OUT_OF_BOUNDS; }
-          else { index = index * 10 + digit; }
-        }
-        if (tl == 0) { q.arr_code = QUERY_INVALID_JSON_POINTER; }
-        q.arr_index = q.arr_code ? 0 : index;
-      }
-      // by a scalar: the rest from this token's slash on
-      q.scalar_code = QUERY_NO_SUCH_FIELD;
-      for (uint32_t j = slash; j < L; j++) {
-        if (p[j] != '~') { continue; }
-        if (j + 1 == L || (p[j + 1] != '0' && p[j + 1] != '1')) { q.scalar_code = QUERY_INVALID_JSON_POINTER; }
-        break;
-      }
-      toks.push_back(q);
-      qp.tokens++;
-      slash = end;
-    }
+    if (!append_pointer_tokens(p, L, qp.keys_at, QUERY_MAX_TOKENS, &toks, &keys, &qp.tokens)) { return false; }
   }
   out->tokens_at = uint32_t(K * sizeof(query_pointer));
   out->keys_at = uint32_t(out->tokens_at + toks.size() * sizeof(query_token));

@@ -1,9 +1,10 @@
-// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h and include/sjgpu_query.h, what follows the structural list on the device: the strings of a
+// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h, include/sjgpu_query.h and include/sjgpu_paths.h, what follows the structural list on the device: the strings of a
 // document, On-Demand's raw key comparison, stage 2 (the DOM tape of a document, the tapes of a document stream), sjgpu_parse and sjgpu_parse_many, and the queries over the tapes
 // (JSON pointers -> typed columns, a string column -> offsets + characters).  Shared with the other units: sjgpu_ctx.h.
 #include "sjgpu_ctx.h"
 #include "sjgpu_query.h"
-#include "sj_query_program.h"
+#include "sjgpu_paths.h"
+#include "sj_path_program.h"
 
 extern "C" {
 
@@ -413,6 +414,77 @@ int sjgpu_gather_strings_device(sjgpu_ctx *ctx, const void *string_buf_dev, uint
   launch_gather_copy(static_cast<const uint8_t *>(string_buf_dev), value, offsets, docs, bytes, static_cast<uint8_t *>(chars_dev), s);
   SJ_TRY(ctx, hipGetLastError());
   SJ_TRY(ctx, hipStreamSynchronize(s));
+  return 0;
+}
+
+// ---- paths with wildcards over device tapes (k_at_paths in sjgpu_query.hip) ------------------------------------------------------------------------
+int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                          const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev, uint64_t match_cap,
+                          void *stream, uint64_t *matches_out) {
+  if (matches_out) { *matches_out = 0; }
+  if (!ctx || !tape_dev || !string_buf_dev || !docs_dev || !offsets_dev || !matches_out || (K && (!paths || !path_lens)) || (K && docs && !status_dev) ||
+      (match_cap && (!value_dev || !tag_dev))) {
+    return SJGPU_E_BADARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(tape_dev) & 7u) || (reinterpret_cast<uintptr_t>(value_dev) & 7u) || (reinterpret_cast<uintptr_t>(docs_dev) & 15u) ||
+      (reinterpret_cast<uintptr_t>(offsets_dev) & 3u)) {
+    return SJGPU_E_BADARG;
+  }
+  if (tape_words > 0xFFFFFFFFull || string_bytes > 0xFFFFFFFFull || docs >= 0xFFFFFFF0u) { return SJGPU_E_BADARG; } // the table's words are 32 bits
+  path_program prog;
+  if (!compile_path_program(paths, path_lens, K, &prog)) { return SJGPU_E_BADARG; }
+  if (uint64_t(K) * docs + 1 > 0xFFFFFFF0ull) { return SJGPU_E_BADARG; } // the scan's entries are indexed by 32-bit words
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick(ctx, stream);
+  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  if (K == 0 || docs == 0) {
+    SJ_TRY(ctx, hipMemsetAsync(offsets, 0, sizeof(uint32_t), s));
+    SJ_TRY(ctx, hipStreamSynchronize(s));
+    return 0;
+  }
+  // the blocks are the context's: the walk of the previous call must have read its program before it is overwritten
+  if (ctx->query_in_flight) {
+    SJ_TRY(ctx, hipEventSynchronize(ctx->ev_query));
+    ctx->query_in_flight = false;
+  }
+  const size_t block = 256 + prog.bytes.size(); // [0] the table check's word, [256] the program
+  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, block);
+  if (rc) { return rc; }
+  rc = ensure_tmp(ctx, paths_workspace_bytes(K, docs));
+  if (rc) { return rc; }
+  if (ctx->h_query_bytes < block) {
+    if (ctx->h_query) { (void)hipHostFree(ctx->h_query); ctx->h_query = nullptr; ctx->h_query_bytes = 0; }
+    SJ_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_query), block, hipHostMallocDefault));
+    ctx->h_query_bytes = block;
+  }
+  std::memset(ctx->h_query, 0, 256);
+  std::memcpy(ctx->h_query + 256, prog.bytes.data(), prog.bytes.size());
+  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
+  const uint64_t *tape = static_cast<const uint64_t *>(tape_dev);
+  const uint8_t *sbuf = static_cast<const uint8_t *>(string_buf_dev);
+  SJ_TRY(ctx, hipMemcpyAsync(ctx->d_query, ctx->h_query, block, hipMemcpyHostToDevice, s));
+  launch_query_check_table(table, docs, tape_words, string_bytes, reinterpret_cast<uint32_t *>(ctx->d_query), s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint32_t *const bad = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192); // (the pinned block's last slot, as in sjgpu_at_pointers_device)
+  SJ_TRY(ctx, hipMemcpyAsync(bad, ctx->d_query, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  if (*bad) { return SJGPU_E_BADARG; }
+  const void *total_dev = launch_paths_count(tape, sbuf, table, docs, ctx->d_query + 256, prog.levels_at, prog.tokens_at, prog.keys_at, K, offsets,
+                                             static_cast<uint8_t *>(status_dev), ctx->d_tmp, s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
+  SJ_TRY(ctx, hipMemcpyAsync(total, total_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  const uint64_t matches = *total;
+  *matches_out = matches;
+  if (matches > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
+  if (matches > match_cap) { return SJGPU_E_OVERFLOW; }
+  if (matches) {
+    launch_paths_fill(tape, sbuf, table, docs, ctx->d_query + 256, prog.levels_at, prog.tokens_at, prog.keys_at, K, offsets, static_cast<uint64_t *>(value_dev),
+                      static_cast<uint8_t *>(tag_dev), s);
+    SJ_TRY(ctx, hipGetLastError());
+    SJ_TRY(ctx, hipStreamSynchronize(s)); // (the program block and the workspace are free again when the call returns)
+  }
   return 0;
 }
 

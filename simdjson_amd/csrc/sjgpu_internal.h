@@ -294,6 +294,16 @@ size_t gather_workspace_bytes(uint32_t docs);
 const void *launch_gather_offsets(const uint64_t *value, const uint8_t *tag, uint32_t docs, uint64_t string_bytes, uint32_t *offsets, void *workspace, hipStream_t s);
 // total: what the host read back and found to fit chars
 void launch_gather_copy(const uint8_t *string_buf, const uint64_t *value, const uint32_t *offsets, uint32_t docs, uint64_t total, uint8_t *chars, hipStream_t s);
+// ---- paths with wildcards over device tapes (sjgpu_query.hip: sjgpu_at_paths_device) ---------------------------------------------------------------
+// program: what compile_path_program (sj_path_program.h) left, in device memory, 16-byte aligned; K >= 1, docs >= 1, K * docs + 1 entries the scan takes;
+// a table that passed the check.  launch_paths_count: status[c] and, in offsets[0 .. K * docs], the exclusive sum of the cells' match counts;
+// -> the device address of the 64-bit total (workspace: paths_workspace_bytes(K, docs), 256-byte aligned).
+size_t paths_workspace_bytes(uint32_t K, uint32_t docs);
+const void *launch_paths_count(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t levels_at,
+                               uint32_t tokens_at, uint32_t keys_at, uint32_t K, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s);
+// behind it, when the total fits: match j of cell c to value / tag[offsets[c] + j], never at or beyond offsets[c + 1]
+void launch_paths_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t levels_at, uint32_t tokens_at,
+                       uint32_t keys_at, uint32_t K, const uint32_t *offsets, uint64_t *value, uint8_t *tag, hipStream_t s);
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);

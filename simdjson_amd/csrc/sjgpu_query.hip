@@ -22,7 +22,7 @@
 // in 64 bits beside it (per-block sums, then one workgroup), and a copy that is parallel over the OUTPUT: a lane owns 16 bytes of it, finds the cell of its first byte by a search
 // in the offsets and follows the cells from there -- a string of 100 KiB is 6 400 lanes' work, not one lane's.
 #include "sjgpu_device.h"
-#include "sj_query_program.h"
+#include "sj_path_program.h"
 
 namespace sjgpu {
 namespace {
@@ -53,6 +53,76 @@ __device__ __forceinline__ bool key_equals(const u8 *__restrict__ rec, const u8 
     if (rec[j] != key[j]) { return false; }
   }
   return true;
+}
+
+// One at_pointer: the tokens tok[0 .. n) asked of the element that begins at word `cur` (its word: w) -> 0 with the element found in cur / w, or the
+// reference's code.  limit: the end of what surrounds the element (the document, or the container whose child it is); no level is followed beyond it.
+// The loop of k_at_pointers and of every PTR / TAIL level of k_at_paths.
+__device__ __forceinline__ u32 walk_tokens(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const query_token *tok /* LDS */, u32 n, const u8 *keys /* LDS, 8-byte aligned */,
+                                           u64 base, u64 limit, u64 str_base, u64 str_end, u64 &cur, u64 &w) {
+  for (u32 t = 0; t < n; t++) {
+    const u32 kind = u32(w >> 56);
+    if (kind == '{') {
+      if (tok[t].key_code) { return tok[t].key_code; }
+      const u32 klen = tok[t].key_len;
+      const u8 *key = keys + tok[t].key_off;
+      u64 end = base + (w & LOW32) - 1u; // the closing word
+      end = end < limit ? end : limit;
+      u64 i = cur + 1u;
+      bool found = false;
+      while (i + 1u < end) { // a key word and the first word of its value
+        const u64 kw = tape[i], vw = tape[i + 1u];
+        const u64 rec = str_base + (kw & PAYLOAD);
+        if (rec + 4u <= str_end) {
+          const u32 len = *reinterpret_cast<const u32_unaligned *>(sbuf + rec);
+          if (len == klen && rec + 4u + u64(len) <= str_end && key_equals(sbuf + rec + 4u, key, klen)) {
+            found = true;
+            cur = i + 1u;
+            w = vw;
+            break;
+          }
+        }
+        i = behind(i + 1u, vw, base, end);
+      }
+      if (!found) { return QUERY_NO_SUCH_FIELD; }
+    } else if (kind == '[') {
+      if (tok[t].arr_code) { return tok[t].arr_code; }
+      const u64 want = tok[t].arr_index;
+      u64 end = base + (w & LOW32) - 1u;
+      end = end < limit ? end : limit;
+      u64 i = cur + 1u, ordinal = 0;
+      bool found = false;
+      while (i < end) {
+        const u64 ew = tape[i];
+        if (ordinal == want) {
+          found = true;
+          cur = i;
+          w = ew;
+          break;
+        }
+        ordinal++;
+        i = behind(i, ew, base, end);
+      }
+      if (!found) { return QUERY_INDEX_OUT_OF_BOUNDS; }
+    } else {
+      return tok[t].scalar_code;
+    }
+  }
+  return 0;
+}
+
+// the value word of a cell that holds the element at word `cur` (include/sjgpu_query.h); its tag is w >> 56
+__device__ __forceinline__ u64 cell_value(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 cur, u64 w, u64 base, u64 doc_end, u64 str_base, u64 str_end) {
+  const u32 kind = u32(w >> 56);
+  if (is_number_tag(kind)) { return cur + 1u < doc_end ? tape[cur + 1u] : 0; }
+  if (kind == 't') { return 1; }
+  if (kind == '"') {
+    const u64 rec = str_base + (w & PAYLOAD);
+    const u32 len = rec + 4u <= str_end ? *reinterpret_cast<const u32_unaligned *>(sbuf + rec) : 0u;
+    return (u64(len) << 32) | ((rec + 4u) & LOW32);
+  }
+  if (is_container_tag(kind)) { return ((base + (w & LOW32)) << 32) | cur; }
+  return 0;
 }
 
 // grid: K rows of row_blocks workgroups, row k = pointer k (one dimension: at most 64 * 2^24 workgroups)
@@ -90,71 +160,9 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_pointers(const u64 *__rest
   if (!code) {
     if (cur < doc_end) { w = tape[cur]; } else { code = QUERY_NO_SUCH_FIELD; }
   }
-  for (u32 t = 0; t < qp.tokens && !code; t++) {
-    const u32 kind = u32(w >> 56);
-    if (kind == '{') {
-      if (s_tok[t].key_code) { code = s_tok[t].key_code; break; }
-      const u32 klen = s_tok[t].key_len;
-      const u8 *key = reinterpret_cast<const u8 *>(s_key) + s_tok[t].key_off;
-      u64 end = base + (w & LOW32) - 1u; // the closing word
-      end = end < doc_end ? end : doc_end;
-      u64 i = cur + 1u;
-      bool found = false;
-      while (i + 1u < end) { // a key word and the first word of its value
-        const u64 kw = tape[i], vw = tape[i + 1u];
-        const u64 rec = str_base + (kw & PAYLOAD);
-        if (rec + 4u <= str_end) {
-          const u32 len = *reinterpret_cast<const u32_unaligned *>(sbuf + rec);
-          if (len == klen && rec + 4u + u64(len) <= str_end && key_equals(sbuf + rec + 4u, key, klen)) {
-            found = true;
-            cur = i + 1u;
-            w = vw;
-            break;
-          }
-        }
-        i = behind(i + 1u, vw, base, end);
-      }
-      if (!found) { code = QUERY_NO_SUCH_FIELD; }
-    } else if (kind == '[') {
-      if (s_tok[t].arr_code) { code = s_tok[t].arr_code; break; }
-      const u64 want = s_tok[t].arr_index;
-      u64 end = base + (w & LOW32) - 1u;
-      end = end < doc_end ? end : doc_end;
-      u64 i = cur + 1u, ordinal = 0;
-      bool found = false;
-      while (i < end) {
-        const u64 ew = tape[i];
-        if (ordinal == want) {
-          found = true;
-          cur = i;
-          w = ew;
-          break;
-        }
-        ordinal++;
-        i = behind(i, ew, base, end);
-      }
-      if (!found) { code = QUERY_INDEX_OUT_OF_BOUNDS; }
-    } else {
-      code = s_tok[t].scalar_code;
-    }
-  }
-  u32 out_tag = code;
-  u64 out_value = 0;
-  if (!code) {
-    const u32 kind = u32(w >> 56);
-    out_tag = kind;
-    if (is_number_tag(kind)) {
-      out_value = cur + 1u < doc_end ? tape[cur + 1u] : 0;
-    } else if (kind == 't') {
-      out_value = 1;
-    } else if (kind == '"') {
-      const u64 rec = str_base + (w & PAYLOAD);
-      const u32 len = rec + 4u <= str_end ? *reinterpret_cast<const u32_unaligned *>(sbuf + rec) : 0u;
-      out_value = (u64(len) << 32) | ((rec + 4u) & LOW32);
-    } else if (is_container_tag(kind)) {
-      out_value = ((base + (w & LOW32)) << 32) | cur;
-    }
-  }
+  if (!code) { code = walk_tokens(tape, sbuf, s_tok, qp.tokens, reinterpret_cast<const u8 *>(s_key), base, doc_end, str_base, str_end, cur, w); }
+  const u32 out_tag = code ? code : u32(w >> 56);
+  const u64 out_value = code ? 0 : cell_value(tape, sbuf, cur, w, base, doc_end, str_base, str_end);
   const u64 cell = u64(k) * docs + d;
   tag[cell] = u8(out_tag);
   value[cell] = out_value;
@@ -269,6 +277,147 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_gather_copy(const u8 *__restr
   }
 }
 
+// ---- the paths (include/sjgpu_paths.h) ---------------------------------------------------------------------------------------------------------
+// One lane walks one cell (path k, document d) twice: once to count its matches (FILL = false), once -- behind the scan of the counts -- to write them
+// (FILL = true).  The recursion of at_path_with_wildcard is an iterative depth-first walk over the path's LEVELS (sj_path_program.h): `have` says that
+// the element at cur / w waits for level L; otherwise the topmost frame hands out its next child, or is popped.  A frame is pushed per WILD level that
+// meets a container with children: (cursor of the next child's value, end of the level), document-relative, in LDS as [frame][lane] -- a per-lane array
+// indexed by the stack pointer would live in scratch memory.  The frames' levels and kinds (object: a key word lies in front of every value) are eight
+// bytes of one register.  A container's end is cut to the end of the frame it was reached from, so the children of two siblings never overlap and a
+// cell's work stays linear in the words of its document whatever the tape says.
+// grid: K rows of row_blocks workgroups, row k = path k
+template <bool FILL>
+__global__ __launch_bounds__(QUERY_THREADS) void k_at_paths(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table, u32 docs,
+                                                          const u8 *__restrict__ prog, u32 levels_at, u32 tokens_at, u32 keys_at, u32 row_blocks, u32 *__restrict__ offsets,
+                                                          u8 *__restrict__ status, u64 *__restrict__ block_sums, u64 *__restrict__ value, u8 *__restrict__ tag) {
+  __shared__ query_token s_tok[PATH_MAX_TOKENS];
+  __shared__ u64 s_key[QUERY_KEY_AREA / 8];
+  __shared__ path_level s_lev[PATH_MAX_LEVELS];
+  __shared__ u32 s_cur[PATH_MAX_WILDS][QUERY_THREADS], s_end[PATH_MAX_WILDS][QUERY_THREADS];
+  __shared__ u64 s_sum[QUERY_THREADS / 64];
+  const u32 k = blockIdx.x / row_blocks, row_block = blockIdx.x - k * row_blocks, tid = threadIdx.x;
+  const path_header ph = reinterpret_cast<const path_header *>(prog)[k];
+  {
+    const u32 n_lev = ph.levels < PATH_MAX_LEVELS ? ph.levels : PATH_MAX_LEVELS, n_tok = ph.tokens < PATH_MAX_TOKENS ? ph.tokens : PATH_MAX_TOKENS;
+    const u64 *lsrc = reinterpret_cast<const u64 *>(prog + levels_at) + u64(ph.first_level) * (sizeof(path_level) / 8);
+    u64 *ldst = reinterpret_cast<u64 *>(s_lev);
+    for (u32 j = tid; j < n_lev * u32(sizeof(path_level) / 8); j += QUERY_THREADS) { ldst[j] = lsrc[j]; }
+    const u64 *src = reinterpret_cast<const u64 *>(prog + tokens_at) + u64(ph.first_token) * (sizeof(query_token) / 8);
+    u64 *dst = reinterpret_cast<u64 *>(s_tok);
+    for (u32 j = tid; j < n_tok * u32(sizeof(query_token) / 8); j += QUERY_THREADS) { dst[j] = src[j]; }
+    u32 key_words = 0;
+    if (n_tok) {
+      const query_token last = reinterpret_cast<const query_token *>(prog + tokens_at)[ph.first_token + n_tok - 1u];
+      key_words = (last.key_off + last.key_len + 7u) / 8u;
+    }
+    key_words = key_words < QUERY_KEY_AREA / 8 ? key_words : QUERY_KEY_AREA / 8;
+    const u64 *ksrc = reinterpret_cast<const u64 *>(prog + keys_at + ph.keys_at);
+    for (u32 j = tid; j < key_words; j += QUERY_THREADS) { s_key[j] = ksrc[j]; }
+  }
+  lds_writes_done();
+  __syncthreads();
+  const u64 d64 = u64(row_block) * QUERY_THREADS + tid;
+  const bool active = d64 < docs;
+  const u64 cell = u64(k) * docs + d64;
+  u32 count = 0, code = 0;
+  u64 out = 0, out_end = 0; // FILL: the cell's matches are value / tag[out .. out_end)
+  bool go = active;
+  if (FILL && active) {
+    out = offsets[cell];
+    out_end = offsets[cell + 1u];
+    go = out < out_end; // (a cell without matches, or with a status, has nothing to write)
+  }
+  if (go) {
+    const u32 d = u32(d64);
+    const uint4 a = *reinterpret_cast<const uint4 *>(table + d), b = *reinterpret_cast<const uint4 *>(table + d + 1u);
+    const u64 base = a.z, doc_end = b.z; // the document's words: [base, doc_end)
+    const u64 str_base = a.w, str_end = b.w;
+    const u8 *keys = reinterpret_cast<const u8 *>(s_key);
+    auto emit = [&](u64 at, u64 ew) {
+      if (FILL) {
+        if (out < out_end) { // never at or beyond the next cell's first match, whatever the tape says
+          tag[out] = u8(ew >> 56);
+          value[out] = cell_value(tape, sbuf, at, ew, base, doc_end, str_base, str_end);
+          out++;
+        }
+      } else {
+        count++;
+      }
+    };
+    u64 cur = base + 1u; // the root: behind the root word
+    u64 w = cur < doc_end ? tape[cur] : 0; // (no root: a tag that is no container's)
+    u32 L = 0, sp = 0;
+    u64 frames = 0; // byte s: the level of frame s, bit 7: the frame walks an object
+    bool have = true;
+    for (;;) {
+      if (have) {
+        have = false;
+        const u32 kind = u32(w >> 56);
+        if (!is_container_tag(kind)) { continue; } // a scalar contributes nothing at any level, and is no error
+        const u64 limit = sp ? base + s_end[sp - 1u][tid] : doc_end;
+        const path_level lv = s_lev[L];
+        if (lv.kind == PATH_PTR || lv.kind == PATH_TAIL) {
+          const u32 c = walk_tokens(tape, sbuf, s_tok + lv.first_token, lv.tokens, keys, base, limit, str_base, str_end, cur, w);
+          if (lv.kind == PATH_PTR) {
+            if (!c && L + 1u < ph.levels) { L++; have = true; }
+          } else if (c) {
+            if (L == 0) { code = c; }
+          } else {
+            emit(cur, w);
+          }
+        } else if (lv.kind == PATH_WILD || lv.kind == PATH_WILD_LAST) {
+          const u32 obj = kind == '{' ? 1u : 0u;
+          u64 end = base + (w & LOW32);
+          end = end > cur ? end - 1u : cur; // the closing word
+          end = end < limit ? end : limit;
+          u64 i = cur + 1u + obj; // the first child's value
+          if (lv.kind == PATH_WILD_LAST) {
+            while (i < end) {
+              const u64 ew = tape[i];
+              emit(i, ew);
+              i = behind(i, ew, base, end) + obj;
+            }
+          } else if (i < end && sp < PATH_MAX_WILDS && L + 1u < ph.levels) {
+            s_cur[sp][tid] = u32(i - base);
+            s_end[sp][tid] = u32(end - base);
+            frames = (frames & ~(0xFFull << (8u * sp))) | (u64(L | (obj << 7)) << (8u * sp));
+            sp++;
+          }
+        } else if (L == 0) {
+          code = QUERY_INVALID_JSON_POINTER; // ERR22
+        }
+      } else {
+        if (sp == 0) { break; }
+        const u32 f = u32(frames >> (8u * (sp - 1u))) & 0xFFu;
+        const u64 end = base + s_end[sp - 1u][tid], i = base + s_cur[sp - 1u][tid];
+        if (i < end) {
+          cur = i;
+          w = tape[i];
+          const u64 next = behind(i, w, base, end) + (f >> 7);
+          s_cur[sp - 1u][tid] = u32((next < end ? next : end) - base);
+          L = (f & 31u) + 1u;
+          have = true;
+        } else {
+          sp--;
+        }
+      }
+    }
+  }
+  if (FILL) { return; }
+  if (active) {
+    offsets[cell] = code ? 0u : count;
+    status[cell] = u8(code);
+    if (cell == 0) { offsets[u64(gridDim.x / row_blocks) * docs] = 0; } // the scan's last entry: the total lands there
+  }
+  u64 sum = code ? 0u : count;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); }
+  if (lane_id() == 0) { s_sum[tid >> 6] = sum; }
+  lds_writes_done();
+  __syncthreads();
+  if (tid == 0) { block_sums[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]; }
+}
+
 static inline u32 blocks_of(u64 n, u32 per) { return u32((n + per - 1) / per); }
 
 } // namespace
@@ -302,6 +451,31 @@ const void *launch_gather_offsets(const uint64_t *value, const uint8_t *tag, uin
 void launch_gather_copy(const uint8_t *string_buf, const uint64_t *value, const uint32_t *offsets, uint32_t docs, uint64_t total, uint8_t *chars, hipStream_t s) {
   if (total == 0 || docs == 0) { return; }
   hipLaunchKernelGGL(k_gather_copy, dim3(blocks_of(total, QUERY_THREADS * GATHER_CHUNK)), dim3(QUERY_THREADS), 0, s, string_buf, value, offsets, docs, total, chars);
+}
+
+// [ctrl, 256 bytes][the count kernel's block sums][the scan's block sums]
+static inline size_t paths_sums_bytes(uint32_t K, uint32_t docs) { return (size_t(blocks_of(docs, QUERY_THREADS)) * K * sizeof(u64) + 255) & ~size_t(255); }
+size_t paths_workspace_bytes(uint32_t K, uint32_t docs) { return 256 + paths_sums_bytes(K, docs) + (size_t(blocks_of(u64(K) * docs + 1, 4096)) + 64) * sizeof(int); }
+
+const void *launch_paths_count(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t levels_at,
+                               uint32_t tokens_at, uint32_t keys_at, uint32_t K, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s) {
+  uint8_t *ws = static_cast<uint8_t *>(workspace);
+  gather_ctrl *ctrl = reinterpret_cast<gather_ctrl *>(ws);
+  u64 *block_sums = reinterpret_cast<u64 *>(ws + 256);
+  int *partial = reinterpret_cast<int *>(ws + 256 + paths_sums_bytes(K, docs));
+  const u32 row_blocks = blocks_of(docs, QUERY_THREADS), cells = K * docs;
+  hipLaunchKernelGGL(k_at_paths<false>, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, docs, program, levels_at, tokens_at, keys_at, row_blocks, offsets,
+                     status, block_sums, static_cast<u64 *>(nullptr), static_cast<u8 *>(nullptr));
+  hipLaunchKernelGGL(k_gather_total, dim3(1), dim3(QUERY_THREADS), 0, s, block_sums, row_blocks * K, cells, ctrl);
+  enqueue_scan(reinterpret_cast<int *>(offsets), cells + 1u, &ctrl->n_plus_1, partial, s);
+  return ctrl;
+}
+
+void launch_paths_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t levels_at, uint32_t tokens_at,
+                       uint32_t keys_at, uint32_t K, const uint32_t *offsets, uint64_t *value, uint8_t *tag, hipStream_t s) {
+  const u32 row_blocks = blocks_of(docs, QUERY_THREADS);
+  hipLaunchKernelGGL(k_at_paths<true>, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, docs, program, levels_at, tokens_at, keys_at, row_blocks,
+                     const_cast<u32 *>(offsets), static_cast<u8 *>(nullptr), static_cast<u64 *>(nullptr), value, tag);
 }
 
 } // namespace sjgpu
