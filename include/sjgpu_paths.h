@@ -57,12 +57,43 @@ extern "C" {
  * fill (the same walk, writing).  Waits for the stream: the total is read back, and the columns are complete on return.
  * Cost, not hidden: one lane walks one cell, consecutive lanes consecutive documents of one path.  A cell costs time linear in the
  * siblings it passes and in the elements it visits under its wildcards, twice, and all of it is ONE lane's work: `$.statuses[*].user.id`
- * over one large document runs on one lane.  The fill's stores are one run per lane, not coalesced across lanes.  There is no
- * frontier-per-level (breadth-first) expansion that would share one document among lanes. */
+ * over one large document runs on one lane.  The fill's stores are one run per lane, not coalesced across lanes.  The
+ * frontier-per-level (breadth-first) expansion that shares one document among lanes is sjgpu_at_paths_wide_device below. */
 int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes,
                           const void *docs_dev, uint32_t docs, const uint8_t *paths, const uint32_t *path_lens, uint32_t K,
                           void *offsets_dev /* K * docs + 1 u32 */, void *status_dev /* K * docs bytes */,
                           void *value_dev, void *tag_dev, uint64_t match_cap, void *stream, uint64_t *matches_out);
+
+/* ---- the same column, breadth first (the k_wide_* kernels in sjgpu_query.hip) ------------------------------------------------------
+ * The contract of sjgpu_at_paths_device, word for word: the cells, the level program and its limits, the alignments and refusals, K == 0 /
+ * docs == 0, CAPACITY for a total beyond 32 bits, SJGPU_E_OVERFLOW with offsets_dev and status_dev complete, *matches_out set and nothing
+ * written to value_dev / tag_dev, nothing written outside the contracted ranges, nothing read outside the three arrays, and the call
+ * waits for the stream.  Over tapes that sjgpu_stage2_device / sjgpu_stage2_many_device delivered all four outputs are bit for bit those
+ * of sjgpu_at_paths_device.  Over words that are no tape the results are unspecified; the call still ends, stays inside its arrays and
+ * never writes at or beyond match_cap.
+ * How: the elements of ALL documents that wait for a level of a path are one ascending list of tape indices, and a level turns that
+ * list into the next.  `.key` levels and the pointer behind the last `*` take one lane per element of the list.  A wildcard level lays
+ * the words of the list's containers end to end and takes one lane per WORD: a word is a child when it begins an element one nesting
+ * level below its container, which an annotation of the tape (a bit and a depth per word, made once per call for all K paths) answers
+ * without a walk.  The match list of a path is ascending, so the cells of its documents are slices of it found by a search.
+ * Capacity: the levels run twice -- once for statuses, offsets and the total, once more to write when the total fits -- except for the
+ * last path, whose matches are still in the workspace; with K == 1 they run once.
+ * Workspace (the context's, grown on demand; its failure is SJGPU_E_NOMEM): 25 bytes per tape word -- annotation 5, two
+ * lists 8, the wildcard level's extents, child ranks and counts 12 -- plus 4 per document and the scans' block sums, whatever K is:
+ * the tapes of a 256 MiB document of 40 M words ask for 1 GB.
+ * Costs, not hidden:
+ *   the annotation is linear in tape_words, once per call, whatever the paths touch;
+ *   a wildcard level is linear in the summed extents (closing word - opening word - 1) of the list's containers, spread over lanes:
+ *   `$.statuses[*].user.id` looks at every word of the document once per run, with as many lanes as there are words;
+ *   a `.key` / pointer level is still ONE lane per element, linear in the siblings it passes: a key searched in one object of a million
+ *   fields stays one lane's work;
+ *   every path costs a handful of launches per level and one 4-byte read-back the host waits for per `.key` level, two per wildcard
+ *   level.  For streams of small records sjgpu_at_paths_device is therefore expected to stay the faster call; that is not measured.
+ * Which of the two calls to take is the caller's decision: choosing automatically needs the measured crossover, and is not built. */
+int sjgpu_at_paths_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes,
+                               const void *docs_dev, uint32_t docs, const uint8_t *paths, const uint32_t *path_lens, uint32_t K,
+                               void *offsets_dev /* K * docs + 1 u32 */, void *status_dev /* K * docs bytes */,
+                               void *value_dev, void *tag_dev, uint64_t match_cap, void *stream, uint64_t *matches_out);
 
 #ifdef __cplusplus
 }

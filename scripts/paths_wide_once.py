@@ -1,0 +1,151 @@
+"""One measurement of the two roads of the paths over device tapes: sjgpu_at_paths_device (one lane per cell) beside sjgpu_at_paths_wide_device
+(breadth first, one lane per word of a wildcard level), in the manner of scripts/paths_once.py.
+
+Per case one process, warmed, alternating, events on the stream, median and min of --reps:
+  the sjgpu_stage2_many_device that made the tapes, the narrow call, the wide call -- the two calls at the exact capacity a first call asked for.
+Cases:
+  one twitter-like document of --twitter-mib MiB (several sizes may be given):
+    $.statuses[*].user.id
+    $.statuses[*].entities.hashtags[*].text              the path as real tweets have it; the synthetic corpus keeps `entities` under `user` and its
+                                                         hashtags hold only `indices`, so this one matches nothing: every branch ends at `.entities`
+    $.statuses[*].user.entities.hashtags[*].indices[*]   the nearest path that matches in the corpus: three wildcard levels
+  the amazon-like NDJSON of --mib MiB (scripts/query_once.py's: every record an array of nine scalars):
+    $[*]
+The outputs of the two calls are compared once, bit for bit, before anything is timed.  Writes --out (profiles/paths_wide.txt) and prints the same JSON
+line.  For the split into kernels run it once more under `rocprofv3 --kernel-trace --stats` with --reps 3 (tracing slows the host: the timings of that
+run are not the ones to quote)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np  # noqa: E402
+
+from simdjson_amd import build, capi, corpus  # noqa: E402
+
+TWITTER_PATHS = [b"$.statuses[*].user.id", b"$.statuses[*].entities.hashtags[*].text", b"$.statuses[*].user.entities.hashtags[*].indices[*]"]
+
+
+class Resident:
+    """a host buffer's stage 1 and its tapes (one per document), everything on the device, and what running stage 2 again needs"""
+
+    def __init__(self, torch, host, doc_cap):
+        self.p = p = capi.DomParserImplementation(len(host) + 64)
+        self.s = s = torch.cuda.current_stream().cuda_stream
+        self.length = len(host)
+        self.buf = torch.from_numpy(np.concatenate([host, np.zeros(64, np.uint8)])).cuda()
+        self.idx = torch.zeros(len(host) + 16, dtype=torch.int32, device="cuda")
+        assert p.stage1_device(self.buf.data_ptr(), len(host), self.idx.data_ptr(), len(host) + 3, s) == 0
+        self.n, flags, _ = p.result(s)
+        assert flags == 0, flags
+        self.sbuf = torch.empty(5 * (len(host) // 3) + 256, dtype=torch.uint8, device="cuda")
+        self.tape = torch.empty(min(4 * self.n, len(host) + 3 * doc_cap) + 8, dtype=torch.int64, device="cuda")
+        self.table = torch.empty((doc_cap + 1) * 4, dtype=torch.int32, device="cuda")
+        code, self.docs, self.tw, self.sb = self.stage2()
+        assert code == 0, code
+
+    def stage2(self):
+        return self.p.stage2_many_device(self.buf.data_ptr(), self.length, self.idx.data_ptr(), self.n, self.tape.data_ptr(), self.tape.numel(), self.sbuf.data_ptr(),
+                                         self.sbuf.numel(), self.table.data_ptr(), self.table.numel() // 4, stream=self.s)
+
+
+def roads(R, torch, paths):
+    """-> (narrow, wide, matches): the two calls into outputs of the size a first call asked for, compared bit for bit once"""
+    cells = len(paths) * R.docs
+    args = (R.tape.data_ptr(), R.tw, R.sbuf.data_ptr(), R.sb, R.table.data_ptr(), R.docs, paths)
+    rc, matches = R.p.at_paths_device(*args, torch.empty(cells + 1, dtype=torch.int32, device="cuda").data_ptr(), torch.empty(cells, dtype=torch.uint8, device="cuda").data_ptr(),
+                                      0, 0, 0, R.s)
+    assert rc in (0, -5), rc
+    outs, fns = [], []
+    for call in (R.p.at_paths_device, R.p.at_paths_wide_device):
+        out = (torch.zeros(cells + 1, dtype=torch.int32, device="cuda"), torch.zeros(cells, dtype=torch.uint8, device="cuda"),
+               torch.zeros(max(matches, 1), dtype=torch.int64, device="cuda"), torch.zeros(max(matches, 1), dtype=torch.uint8, device="cuda"))
+
+        def run(call=call, out=out):
+            rc, m = call(*args, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), matches, R.s)
+            assert (rc, m) == (0, matches), (rc, m)
+        run()
+        outs.append(out)
+        fns.append(run)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(*outs)), "the two roads disagree"
+    return fns[0], fns[1], matches
+
+
+def stage2_again(R):
+    def run():
+        assert R.stage2() == (0, R.docs, R.tw, R.sb)
+    return run
+
+
+def measure(torch, runs, reps, warmup):
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+    for _ in range(warmup):
+        for fn in runs.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in runs}
+    for _ in range(reps):  # alternating: what the clock and the neighbours do hits all alike
+        for name, fn in runs.items():
+            times[name].append(timed(fn))
+    return {name: {"median": round(statistics.median(t), 3), "min": round(min(t), 3), "max": round(max(t), 3)} for name, t in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mib", type=int, default=256)
+    ap.add_argument("--twitter-mib", type=int, nargs="*", default=[64])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "paths_wide.txt"))
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: this script measures, it does not fall back")
+    build.build_sjgpu()
+    out = {"reps": args.reps, "unit": "ms", "cases": []}
+    for mib in args.twitter_mib:
+        host, statuses = corpus.twitter_like(mib << 20, 7)
+        R = Resident(torch, host, 1)
+        assert R.docs == 1
+        for path in TWITTER_PATHS:
+            narrow, wide, matches = roads(R, torch, [path])
+            case = {"corpus": "twitter-like, one document", "mib": round(len(host) / 2 ** 20, 1), "tape_words": int(R.tw), "statuses": int(statuses), "path": path.decode(),
+                    "matches": int(matches)}
+            case.update(measure(torch, {"stage2_many": stage2_again(R), "narrow": narrow, "wide": wide}, args.reps, args.warmup))
+            case["wide_min_over_narrow_min"] = round(case["wide"]["min"] / case["narrow"]["min"], 4)
+            out["cases"].append(case)
+            print(json.dumps(case), flush=True)
+        R.p.close()
+        del R
+        torch.cuda.empty_cache()
+    if args.mib:
+        host, lines = corpus.amazon_ndjson(args.mib << 20, 7)
+        R = Resident(torch, host, lines + 1)
+        assert R.docs == lines
+        narrow, wide, matches = roads(R, torch, [b"$[*]"])
+        case = {"corpus": "amazon-like NDJSON", "mib": round(len(host) / 2 ** 20, 1), "tape_words": int(R.tw), "records": int(R.docs), "path": "$[*]", "matches": int(matches)}
+        case.update(measure(torch, {"stage2_many": stage2_again(R), "narrow": narrow, "wide": wide}, args.reps, args.warmup))
+        case["wide_min_over_narrow_min"] = round(case["wide"]["min"] / case["narrow"]["min"], 4)
+        out["cases"].append(case)
+        print(json.dumps(case), flush=True)
+        R.p.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("scripts/paths_wide_once.py: sjgpu_at_paths_device (narrow) beside sjgpu_at_paths_wide_device (wide), milliseconds, median / min / max of %d, one process, warmed, "
+                "alternating, events on the stream\n" % args.reps)
+        for case in out["cases"]:
+            f.write(json.dumps(case) + "\n")
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -57,7 +57,7 @@ INCORRECT_TYPE, INDEX_OUT_OF_BOUNDS, NO_SUCH_FIELD, INVALID_JSON_POINTER = 17, 1
 
 
 # what include/sjgpu_paths.h declares (JSONPath with wildcards over device tapes: one ragged column, CSR style)
-PATH_EXPORTS = ["sjgpu_at_paths_device"]
+PATH_EXPORTS = ["sjgpu_at_paths_device", "sjgpu_at_paths_wide_device"]
 
 
 class ScanResult(ctypes.Structure):
@@ -155,6 +155,8 @@ def load_library():
     L.sjgpu_gather_strings_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_at_paths_device.restype = ctypes.c_int
     L.sjgpu_at_paths_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint64, vp, u64p]
+    L.sjgpu_at_paths_wide_device.restype = ctypes.c_int
+    L.sjgpu_at_paths_wide_device.argtypes = L.sjgpu_at_paths_device.argtypes
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int
@@ -542,20 +544,29 @@ class DomParserImplementation:
     def at_paths_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap, stream=0):
         """sjgpu_at_paths_device: paths = list of bytes (JSONPath, wildcards allowed); offsets_ptr -> len(paths) * docs + 1 uint32, status_ptr -> len(paths) * docs bytes,
         value_ptr / tag_ptr -> match_cap uint64 / bytes.  -> (code, matches): 0, CAPACITY or a negative SJGPU_E_* (raises on HIP errors)"""
+        return self._at_paths("sjgpu_at_paths_device", tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap,
+                              stream)
+
+    def at_paths_wide_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap, stream=0):
+        """sjgpu_at_paths_wide_device: the arguments and results of at_paths_device, the levels expanded breadth first (one large document is many lanes' work)"""
+        return self._at_paths("sjgpu_at_paths_wide_device", tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr,
+                              match_cap, stream)
+
+    def _at_paths(self, name, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap, stream):
         blob = b"".join(paths)
         lens = np.array([len(x) for x in paths], dtype=np.uint32)
         matches = ctypes.c_uint64(0)
-        rc = self.L.sjgpu_at_paths_device(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs),
-                                          ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(paths), offsets_ptr, status_ptr or None,
-                                          value_ptr or None, tag_ptr or None, int(match_cap), stream or None, ctypes.byref(matches))
+        rc = getattr(self.L, name)(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs),
+                                   ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(paths), offsets_ptr, status_ptr or None,
+                                   value_ptr or None, tag_ptr or None, int(match_cap), stream or None, ctypes.byref(matches))
         if rc in (-2, -3):
-            raise SjgpuError(f"sjgpu_at_paths_device error {rc}: {self.last_error()}")
+            raise SjgpuError(f"{name} error {rc}: {self.last_error()}")
         return rc, int(matches.value)
 
-    def explode_many(self, data, paths, max_depth=1024, first_cap=None):
+    def explode_many(self, data, paths, max_depth=1024, first_cap=None, wide=False):
         """The arrays of every record as one ragged column: upload, stage 1, sjgpu_stage2_many_device and sjgpu_at_paths_device with everything resident (the twin of
         extract_many).  At most two calls of sjgpu_at_paths_device: a second one with the capacity the first reported (first_cap: the first call's guess, by default one
-        match per tape word in eight).
+        match per tape word in eight).  wide: sjgpu_at_paths_wide_device in its place (the same column; the choice is the caller's).
         -> (error_code of the first broken document or 0, documents delivered, status uint8[K, docs], offsets uint32[K * docs + 1], tags uint8[matches], values uint64[matches])"""
         import torch
         a = _as_u8(data)
@@ -585,16 +596,17 @@ class DomParserImplementation:
         offsets = torch.empty(K * docs + 1, dtype=torch.int32, device=dev)
         status = torch.empty((K, docs), dtype=torch.uint8, device=dev)
         cap = int(tw // 8 + 1 if first_cap is None else first_cap)
+        at_paths = self.at_paths_wide_device if wide else self.at_paths_device
         for attempt in range(2):
             values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
             tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            rc, matches = self.at_paths_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, paths, offsets.data_ptr(), status.data_ptr(), values.data_ptr(),
-                                               tags.data_ptr(), cap, stream)
+            rc, matches = at_paths(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, paths, offsets.data_ptr(), status.data_ptr(), values.data_ptr(),
+                                   tags.data_ptr(), cap, stream)
             if rc != -5:  # SJGPU_E_OVERFLOW: once more, with what it asks for
                 break
             cap = matches
         if rc:
-            raise SjgpuError(f"sjgpu_at_paths_device refused its arguments ({rc})")
+            raise SjgpuError(f"sjgpu_at_paths{'_wide' if wide else ''}_device refused its arguments ({rc})")
         torch.cuda.current_stream(dev).synchronize()
         return code, docs, status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(), values[:matches].cpu().numpy().view(np.uint64)
 

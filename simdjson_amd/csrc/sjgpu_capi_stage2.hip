@@ -417,10 +417,17 @@ int sjgpu_gather_strings_device(sjgpu_ctx *ctx, const void *string_buf_dev, uint
   return 0;
 }
 
-// ---- paths with wildcards over device tapes (k_at_paths in sjgpu_query.hip) ------------------------------------------------------------------------
-int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
-                          const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev, uint64_t match_cap,
-                          void *stream, uint64_t *matches_out) {
+// ---- paths with wildcards over device tapes (k_at_paths and the k_wide_* kernels in sjgpu_query.hip) -------------------------------------------------
+} // extern "C"
+
+namespace {
+// What sjgpu_at_paths_device and sjgpu_at_paths_wide_device do before their first kernel: the argument checks, the level program, K == 0 / docs == 0, the
+// context's program block and the road's workspace in d_tmp (wide: paths_wide_workspace_bytes, else paths_workspace_bytes), the upload and the table check.  -> 0 with *done = false: the program lies at ctx->d_query + 256 and the
+// table passed; *done = true: the call is over with the code returned.
+int paths_begin(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev, uint64_t match_cap, void *stream,
+                uint64_t *matches_out, bool wide, path_program *prog, hipStream_t *stream_out, bool *done) {
+  *done = true;
   if (matches_out) { *matches_out = 0; }
   if (!ctx || !tape_dev || !string_buf_dev || !docs_dev || !offsets_dev || !matches_out || (K && (!paths || !path_lens)) || (K && docs && !status_dev) ||
       (match_cap && (!value_dev || !tag_dev))) {
@@ -431,14 +438,13 @@ int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_wo
     return SJGPU_E_BADARG;
   }
   if (tape_words > 0xFFFFFFFFull || string_bytes > 0xFFFFFFFFull || docs >= 0xFFFFFFF0u) { return SJGPU_E_BADARG; } // the table's words are 32 bits
-  path_program prog;
-  if (!compile_path_program(paths, path_lens, K, &prog)) { return SJGPU_E_BADARG; }
+  if (!compile_path_program(paths, path_lens, K, prog)) { return SJGPU_E_BADARG; }
   if (uint64_t(K) * docs + 1 > 0xFFFFFFF0ull) { return SJGPU_E_BADARG; } // the scan's entries are indexed by 32-bit words
   SJ_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = pick(ctx, stream);
-  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  *stream_out = s;
   if (K == 0 || docs == 0) {
-    SJ_TRY(ctx, hipMemsetAsync(offsets, 0, sizeof(uint32_t), s));
+    SJ_TRY(ctx, hipMemsetAsync(offsets_dev, 0, sizeof(uint32_t), s));
     SJ_TRY(ctx, hipStreamSynchronize(s));
     return 0;
   }
@@ -447,10 +453,10 @@ int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_wo
     SJ_TRY(ctx, hipEventSynchronize(ctx->ev_query));
     ctx->query_in_flight = false;
   }
-  const size_t block = 256 + prog.bytes.size(); // [0] the table check's word, [256] the program
+  const size_t block = 256 + prog->bytes.size(); // [0] the table check's word, [256] the program
   int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, block);
   if (rc) { return rc; }
-  rc = ensure_tmp(ctx, paths_workspace_bytes(K, docs));
+  rc = ensure_tmp(ctx, wide ? paths_wide_workspace_bytes(K, docs, tape_words) : paths_workspace_bytes(K, docs));
   if (rc) { return rc; }
   if (ctx->h_query_bytes < block) {
     if (ctx->h_query) { (void)hipHostFree(ctx->h_query); ctx->h_query = nullptr; ctx->h_query_bytes = 0; }
@@ -458,17 +464,34 @@ int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_wo
     ctx->h_query_bytes = block;
   }
   std::memset(ctx->h_query, 0, 256);
-  std::memcpy(ctx->h_query + 256, prog.bytes.data(), prog.bytes.size());
-  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
-  const uint64_t *tape = static_cast<const uint64_t *>(tape_dev);
-  const uint8_t *sbuf = static_cast<const uint8_t *>(string_buf_dev);
+  std::memcpy(ctx->h_query + 256, prog->bytes.data(), prog->bytes.size());
   SJ_TRY(ctx, hipMemcpyAsync(ctx->d_query, ctx->h_query, block, hipMemcpyHostToDevice, s));
-  launch_query_check_table(table, docs, tape_words, string_bytes, reinterpret_cast<uint32_t *>(ctx->d_query), s);
+  launch_query_check_table(static_cast<const doc_span_dev *>(docs_dev), docs, tape_words, string_bytes, reinterpret_cast<uint32_t *>(ctx->d_query), s);
   SJ_TRY(ctx, hipGetLastError());
   uint32_t *const bad = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192); // (the pinned block's last slot, as in sjgpu_at_pointers_device)
   SJ_TRY(ctx, hipMemcpyAsync(bad, ctx->d_query, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   SJ_TRY(ctx, hipStreamSynchronize(s));
   if (*bad) { return SJGPU_E_BADARG; }
+  *done = false;
+  return 0;
+}
+} // namespace
+
+extern "C" {
+
+int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                          const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev, uint64_t match_cap,
+                          void *stream, uint64_t *matches_out) {
+  path_program prog;
+  hipStream_t s = nullptr;
+  bool done = true;
+  const int rc = paths_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, paths, path_lens, K, offsets_dev, status_dev, value_dev, tag_dev, match_cap,
+                             stream, matches_out, false, &prog, &s, &done);
+  if (done) { return rc; }
+  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
+  const uint64_t *tape = static_cast<const uint64_t *>(tape_dev);
+  const uint8_t *sbuf = static_cast<const uint8_t *>(string_buf_dev);
   const void *total_dev = launch_paths_count(tape, sbuf, table, docs, ctx->d_query + 256, prog.levels_at, prog.tokens_at, prog.keys_at, K, offsets,
                                              static_cast<uint8_t *>(status_dev), ctx->d_tmp, s);
   SJ_TRY(ctx, hipGetLastError());
@@ -485,6 +508,27 @@ int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_wo
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s)); // (the program block and the workspace are free again when the call returns)
   }
+  return 0;
+}
+
+// the same cells, breadth first: the level loop is launch_paths_wide's (sjgpu_query.hip), which the CPU tier runs too
+int sjgpu_at_paths_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                               const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev,
+                               uint64_t match_cap, void *stream, uint64_t *matches_out) {
+  path_program prog;
+  hipStream_t s = nullptr;
+  bool done = true;
+  const int rc = paths_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, paths, path_lens, K, offsets_dev, status_dev, value_dev, tag_dev, match_cap,
+                             stream, matches_out, true, &prog, &s, &done);
+  if (done) { return rc; }
+  uint32_t *const readback = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
+  uint64_t matches = 0;
+  SJ_TRY(ctx, launch_paths_wide(static_cast<const uint64_t *>(tape_dev), tape_words, static_cast<const uint8_t *>(string_buf_dev), static_cast<const doc_span_dev *>(docs_dev), docs,
+                                ctx->d_query + 256, prog.bytes.data(), prog.levels_at, prog.tokens_at, prog.keys_at, K, static_cast<uint32_t *>(offsets_dev),
+                                static_cast<uint8_t *>(status_dev), static_cast<uint64_t *>(value_dev), static_cast<uint8_t *>(tag_dev), match_cap, ctx->d_tmp, readback, s, &matches));
+  *matches_out = matches;
+  if (matches > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
+  if (matches > match_cap) { return SJGPU_E_OVERFLOW; }
   return 0;
 }
 

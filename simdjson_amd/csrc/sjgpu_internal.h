@@ -304,6 +304,17 @@ const void *launch_paths_count(const uint64_t *tape, const uint8_t *string_buf, 
 // behind it, when the total fits: match j of cell c to value / tag[offsets[c] + j], never at or beyond offsets[c + 1]
 void launch_paths_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t levels_at, uint32_t tokens_at,
                        uint32_t keys_at, uint32_t K, const uint32_t *offsets, uint64_t *value, uint8_t *tag, hipStream_t s);
+// ---- the same cells, breadth first (sjgpu_query.hip: sjgpu_at_paths_wide_device) ------------------------------------------------------------------------
+// The whole call behind the table check, K >= 1 and docs >= 1: the annotation of the tape (a head bit and a nesting depth per word), the starting frontier, the
+// levels of every path with their 4-byte read-backs of frontier sizes (into *readback: host memory, pinned where the copy is a real one), statuses, offsets and
+// the total in *matches_out; then, when the total fits match_cap and 32 bits, the levels once more for every path but the last (whose list is still there) and
+// the matches into value / tag.  Waits for the stream.  program / program_host: compile_path_program's bytes in device memory (16-byte aligned) and on the host.
+// Workspace: 256-byte aligned, 25 bytes per tape word (head 1, depth 4, two frontiers 4 + 4, extents 4, child ranks 4, counts 4) + 4 per document + the scans'
+// block sums; 12 more per document where there are more documents than tape words.  The paths share it, K does not enter.
+size_t paths_wide_workspace_bytes(uint32_t K, uint32_t docs, uint64_t tape_words);
+hipError_t launch_paths_wide(const uint64_t *tape, uint64_t tape_words, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program,
+                             const uint8_t *program_host, uint32_t levels_at, uint32_t tokens_at, uint32_t keys_at, uint32_t K, uint32_t *offsets, uint8_t *status,
+                             uint64_t *value, uint8_t *tag, uint64_t match_cap, void *workspace, uint32_t *readback, hipStream_t s, uint64_t *matches_out);
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);

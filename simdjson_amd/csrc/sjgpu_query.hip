@@ -418,6 +418,305 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_paths(const u64 *__restric
   if (tid == 0) { block_sums[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]; }
 }
 
+// ---- the paths, wide (include/sjgpu_paths.h: sjgpu_at_paths_wide_device) --------------------------------------------------------------------------
+// The same cells, breadth first: the elements that wait for level L of a path -- of ALL documents -- are one ascending list of tape indices (the FRONTIER),
+// and a level turns one frontier into the next.  PTR / TAIL: one lane per element (walk_tokens), the survivors compacted in order.  WILD / WILD_LAST: the
+// words between the frontier's containers and their closing words are laid end to end (the scanned extents: the RANGE SPACE), one lane per word of it; a
+// word is a child of its container when it begins an element (its HEAD bit) one nesting level below the container.  Both come from the ANNOTATION, made
+// once per call for the whole tape:
+//   head   a word is a number's second word (raw bits, any byte on top) exactly when the word in front of it is a head tagged l, u or d.  Without a walk:
+//          behind a word whose top byte is NOT one of the three comes a head, whatever that word was -- a payload is followed by a head, and a head that is
+//          no number has one word --, and from there heads and payloads alternate while the top bytes keep looking like numbers.  So with mark(j) = j + 1
+//          for a word whose top byte is none of l u d, else 0, and m = the largest mark in front of word i: i is a head iff i - m is even.  The running
+//          maximum is carried across a lane's four words, the wave (shuffles), the workgroup (LDS) and the workgroups (k_wide_ann_summary, k_wide_ann_carry:
+//          a two-level pass, nobody waits for anybody); every document begins with an `r`, so no run crosses into a document.
+//   depth  the exclusive sum over the heads of +1 for { [ and -1 for } ] (enqueue_scan); only differences of two depths are ever looked at.
+// Elements of one frontier lie side by side (every level descends the same number of steps), so a container's words end in front of the next element of
+// the frontier: the extents are cut there, which changes nothing on a tape and keeps the range space within tape_words on anything else.
+constexpr u32 WIDE_LANE_WORDS = 4, WIDE_SHARE = QUERY_THREADS * WIDE_LANE_WORDS; // a lane's and a workgroup's share of the annotation
+
+__device__ __forceinline__ u32 umax32(u32 a, u32 b) { return a > b ? a : b; }
+__device__ __forceinline__ u32 wide_mark(u64 w, u64 i) { return is_number_tag(u32(w >> 56)) ? 0u : u32(i) + 1u; }
+// the document of tape word idx: the LAST d with tape_begin[d] <= idx (idx at or behind tape_begin[0], docs >= 1)
+__device__ __forceinline__ u32 wide_doc_of(const doc_span_dev *__restrict__ table, u32 docs, u32 idx) {
+  u32 lo = 0, hi = docs;
+  while (hi - lo > 1u) {
+    const u32 mid = lo + (hi - lo) / 2u;
+    if (table[mid].tape_begin <= idx) { lo = mid; } else { hi = mid; }
+  }
+  return lo;
+}
+// the container of word r of the range space: the LAST e with start[e] <= r (start[0] = 0; containers without words share their successor's start)
+__device__ __forceinline__ u32 wide_parent_of(const u32 *__restrict__ start, u32 F, u32 r) {
+  u32 lo = 0, hi = F;
+  while (hi - lo > 1u) {
+    const u32 mid = lo + (hi - lo) / 2u;
+    if (start[mid] <= r) { lo = mid; } else { hi = mid; }
+  }
+  return lo;
+}
+
+// share_last[b] = the largest mark of workgroup b's words
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_ann_summary(const u64 *__restrict__ tape, u32 n, u32 *__restrict__ share_last) {
+  __shared__ u32 s_max[QUERY_THREADS / 64];
+  const u64 i0 = u64(blockIdx.x) * WIDE_SHARE + u64(threadIdx.x) * WIDE_LANE_WORDS;
+  u32 m = 0;
+#pragma unroll
+  for (u32 j = 0; j < WIDE_LANE_WORDS; j++) {
+    if (i0 + j < n) { m = umax32(m, wide_mark(tape[i0 + j], i0 + j)); }
+  }
+#pragma unroll
+  for (int x = 1; x < 64; x <<= 1) { m = umax32(m, __shfl_xor(m, x)); }
+  if (lane_id() == 0) { s_max[threadIdx.x >> 6] = m; }
+  lds_writes_done();
+  __syncthreads();
+  if (threadIdx.x == 0) { share_last[blockIdx.x] = umax32(umax32(s_max[0], s_max[1]), umax32(s_max[2], s_max[3])); }
+}
+// one workgroup, in place: share_last[b] becomes the largest mark IN FRONT of workgroup b's words
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_ann_carry(u32 *__restrict__ share_last, u32 shares) {
+  __shared__ u32 s_part[QUERY_THREADS];
+  const u32 per = (shares + QUERY_THREADS - 1u) / QUERY_THREADS;
+  const u32 lo = min(threadIdx.x * per, shares), hi = min(lo + per, shares);
+  u32 m = 0;
+  for (u32 i = lo; i < hi; i++) { m = umax32(m, share_last[i]); }
+  s_part[threadIdx.x] = m;
+  lds_writes_done();
+  __syncthreads();
+  u32 run = 0;
+  for (u32 t = 0; t < threadIdx.x; t++) { run = umax32(run, s_part[t]); }
+  for (u32 i = lo; i < hi; i++) {
+    const u32 x = share_last[i];
+    share_last[i] = run;
+    run = umax32(run, x);
+  }
+}
+// head[i] and, in depth[i], the word's +1 / -1 / 0 (the scan behind this kernel makes it the depth); *scan_n = n
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_annotate(const u64 *__restrict__ tape, u32 n, const u32 *__restrict__ share_carry, u8 *__restrict__ head,
+                                                               int *__restrict__ depth, u32 *__restrict__ scan_n) {
+  __shared__ u32 s_wave[QUERY_THREADS / 64];
+  const u64 i0 = u64(blockIdx.x) * WIDE_SHARE + u64(threadIdx.x) * WIDE_LANE_WORDS;
+  u64 w[WIDE_LANE_WORDS];
+  u32 mk[WIDE_LANE_WORDS], m = 0;
+#pragma unroll
+  for (u32 j = 0; j < WIDE_LANE_WORDS; j++) {
+    w[j] = i0 + j < n ? tape[i0 + j] : 0;
+    mk[j] = i0 + j < n ? wide_mark(w[j], i0 + j) : 0u;
+    m = umax32(m, mk[j]);
+  }
+  u32 incl = m; // the running maximum over the lanes of the wave (a lane below the distance gets its own value back)
+#pragma unroll
+  for (u32 d = 1; d < 64; d <<= 1) { incl = umax32(incl, __shfl_up(incl, d)); }
+  u32 run = __shfl_up(incl, 1u);
+  if (lane_id() == 0) { run = 0; }
+  if (lane_id() == 63) { s_wave[threadIdx.x >> 6] = incl; }
+  lds_writes_done();
+  __syncthreads();
+  run = umax32(run, share_carry[blockIdx.x]);
+  for (u32 v = 0; v < (threadIdx.x >> 6); v++) { run = umax32(run, s_wave[v]); }
+  u32 heads = 0;
+  int delta[WIDE_LANE_WORDS];
+#pragma unroll
+  for (u32 j = 0; j < WIDE_LANE_WORDS; j++) {
+    const bool is_head = ((u32(i0 + j) - run) & 1u) == 0;
+    const u32 t = u32(w[j] >> 56);
+    delta[j] = !is_head ? 0 : (is_container_tag(t) ? 1 : ((t == '}' || t == ']') ? -1 : 0));
+    heads |= (is_head ? 1u : 0u) << (8u * j);
+    run = umax32(run, mk[j]);
+  }
+  if (i0 + WIDE_LANE_WORDS <= n) {
+    *reinterpret_cast<u32 *>(head + i0) = heads;
+    *reinterpret_cast<int4 *>(depth + i0) = make_int4(delta[0], delta[1], delta[2], delta[3]);
+  } else {
+#pragma unroll
+    for (u32 j = 0; j < WIDE_LANE_WORDS; j++) {
+      if (i0 + j < n) {
+        head[i0 + j] = u8(heads >> (8u * j));
+        depth[i0 + j] = delta[j];
+      }
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) { *scan_n = n; }
+}
+
+// the starting frontier: the documents whose root is a container.  root[d] / flag[d] for d < docs, flag[docs] = 0, *scan_n = docs + 1
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_roots(const u64 *__restrict__ tape, const doc_span_dev *__restrict__ table, u32 docs, u32 *__restrict__ root,
+                                                            int *__restrict__ flag, u32 *__restrict__ scan_n) {
+  const u64 d64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (d64 > docs) { return; }
+  const u32 d = u32(d64);
+  if (d == docs) {
+    flag[d] = 0;
+    *scan_n = docs + 1u;
+    return;
+  }
+  const u64 cur = u64(table[d].tape_begin) + 1u, doc_end = table[d + 1u].tape_begin;
+  root[d] = u32(cur);
+  flag[d] = cur < doc_end && is_container_tag(u32(tape[cur] >> 56)) ? 1 : 0;
+}
+// out[slot[e]] = src[e] for the entries whose flag was set (slot: the exclusive scan of the n + 1 flags)
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_compact(const u32 *__restrict__ src, const int *__restrict__ slot, u32 n, u32 *__restrict__ out) {
+  const u64 e = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (e < n && slot[e + 1u] != slot[e]) { out[slot[e]] = src[e]; }
+}
+// level 0 is an ERR22: INVALID_JSON_POINTER for every container root
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_status(const doc_span_dev *__restrict__ table, u32 docs, const u32 *__restrict__ frontier, u32 F, u32 code,
+                                                             u8 *__restrict__ status_row) {
+  const u64 e = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (e < F) { status_row[wide_doc_of(table, docs, frontier[e])] = u8(code); }
+}
+// a PTR or TAIL level: one lane per element of the frontier.  found[e] / flag[e] for e < F, flag[F] = 0, *scan_n = F + 1; status_row (level 0 of a TAIL,
+// else null): the code of an element that is a root
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_walk(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table, u32 docs,
+                                                           const u8 *__restrict__ prog, u32 tokens_at, u32 keys_at, u32 k, u32 first_token, u32 n_tokens,
+                                                           const u32 *__restrict__ frontier, u32 F, u8 *__restrict__ status_row, u32 *__restrict__ found, int *__restrict__ flag,
+                                                           u32 *__restrict__ scan_n) {
+  __shared__ query_token s_tok[PATH_MAX_TOKENS];
+  __shared__ u64 s_key[QUERY_KEY_AREA / 8];
+  const u32 tid = threadIdx.x;
+  const path_header ph = reinterpret_cast<const path_header *>(prog)[k];
+  {
+    // the path's tokens and key area, as k_at_paths brings them in
+    const u32 n_tok = ph.tokens < PATH_MAX_TOKENS ? ph.tokens : PATH_MAX_TOKENS;
+    const u64 *src = reinterpret_cast<const u64 *>(prog + tokens_at) + u64(ph.first_token) * (sizeof(query_token) / 8);
+    u64 *dst = reinterpret_cast<u64 *>(s_tok);
+    for (u32 j = tid; j < n_tok * u32(sizeof(query_token) / 8); j += QUERY_THREADS) { dst[j] = src[j]; }
+    u32 key_words = 0;
+    if (n_tok) {
+      const query_token last = reinterpret_cast<const query_token *>(prog + tokens_at)[ph.first_token + n_tok - 1u];
+      key_words = (last.key_off + last.key_len + 7u) / 8u;
+    }
+    key_words = key_words < QUERY_KEY_AREA / 8 ? key_words : QUERY_KEY_AREA / 8;
+    const u64 *ksrc = reinterpret_cast<const u64 *>(prog + keys_at + ph.keys_at);
+    for (u32 j = tid; j < key_words; j += QUERY_THREADS) { s_key[j] = ksrc[j]; }
+  }
+  lds_writes_done();
+  __syncthreads();
+  const u64 e64 = u64(blockIdx.x) * QUERY_THREADS + tid;
+  if (e64 > F) { return; }
+  const u32 e = u32(e64);
+  if (e == F) {
+    flag[e] = 0;
+    *scan_n = F + 1u;
+    return;
+  }
+  u64 cur = frontier[e];
+  u64 w = tape[cur];
+  int ok = 0;
+  if (is_container_tag(u32(w >> 56))) { // a scalar contributes nothing at any level, and is no error
+    const u32 d = wide_doc_of(table, docs, u32(cur));
+    const uint4 a = *reinterpret_cast<const uint4 *>(table + d), b = *reinterpret_cast<const uint4 *>(table + d + 1u);
+    u64 limit = b.z; // the end of the document, and -- the frontier's elements lie side by side -- the next element: what is found stays in front of it, so every list ascends
+    if (e + 1u < F) {
+      const u64 next = frontier[e + 1u];
+      limit = limit < next ? limit : next;
+    }
+    const u32 c = walk_tokens(tape, sbuf, s_tok + first_token, n_tokens, reinterpret_cast<const u8 *>(s_key), a.z, limit, a.w, b.w, cur, w);
+    ok = c ? 0 : 1;
+    if (c && status_row) { status_row[d] = u8(c); }
+  }
+  found[e] = u32(cur);
+  flag[e] = ok;
+}
+// a WILD or WILD_LAST level, 1: ext[e] = the words between container e and its closing word (0 for a scalar) for e < F, ext[F] = 0, *scan_n = F + 1
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_extents(const u64 *__restrict__ tape, const doc_span_dev *__restrict__ table, u32 docs, const u32 *__restrict__ frontier,
+                                                              u32 F, int *__restrict__ ext, u32 *__restrict__ scan_n) {
+  const u64 e64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (e64 > F) { return; }
+  const u32 e = u32(e64);
+  if (e == F) {
+    ext[e] = 0;
+    *scan_n = F + 1u;
+    return;
+  }
+  const u64 idx = frontier[e], w = tape[idx];
+  u32 words = 0;
+  if (is_container_tag(u32(w >> 56))) {
+    const u32 d = wide_doc_of(table, docs, u32(idx));
+    const u64 base = table[d].tape_begin, doc_end = table[d + 1u].tape_begin;
+    u64 end = base + (w & LOW32);
+    end = end > idx ? end - 1u : idx; // the closing word
+    end = end < doc_end ? end : doc_end;
+    if (e + 1u < F) { // the next element of the frontier lies behind this one's closing word
+      const u64 next = frontier[e + 1u];
+      end = end < next ? end : next;
+    }
+    words = end > idx + 1u ? u32(end - idx - 1u) : 0u;
+  }
+  ext[e] = int(words);
+}
+// 2: one lane per word of the range space (start: the scanned extents, R = start[F]): child[r] = the word begins a child of its container, child[R] = 0, *scan_n = R + 1
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_children(const u32 *__restrict__ frontier, u32 F, const u32 *__restrict__ start, u32 R, const u8 *__restrict__ head,
+                                                               const int *__restrict__ depth, int *__restrict__ child, u32 *__restrict__ scan_n) {
+  const u64 r64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (r64 > R) { return; }
+  const u32 r = u32(r64);
+  if (r == R) {
+    child[r] = 0;
+    *scan_n = R + 1u;
+    return;
+  }
+  const u32 e = wide_parent_of(start, F, r);
+  const u32 open = frontier[e], i = open + 1u + (r - start[e]);
+  child[r] = head[i] && u32(depth[i]) - u32(depth[open]) == 1u ? 1 : 0;
+}
+// 3: values[e] = the child VALUES of container e (rank: the scanned child flags): an array's children, every second child of an object; values[F] = 0, *scan_n = F + 1
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_counts(const u64 *__restrict__ tape, const u32 *__restrict__ frontier, u32 F, const u32 *__restrict__ start,
+                                                             const int *__restrict__ rank, int *__restrict__ values, u32 *__restrict__ scan_n) {
+  const u64 e64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (e64 > F) { return; }
+  const u32 e = u32(e64);
+  if (e == F) {
+    values[e] = 0;
+    *scan_n = F + 1u;
+    return;
+  }
+  const u32 children = u32(rank[start[e + 1u]]) - u32(rank[start[e]]);
+  values[e] = int(u32(tape[frontier[e]] >> 56) == '{' ? children / 2u : children);
+}
+// 4: the child values in index order into out (first: the scanned counts): child j of an array is its value j, child 2 j + 1 of an object its value j (the even ones are the keys)
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_scatter(const u64 *__restrict__ tape, const u32 *__restrict__ frontier, u32 F, const u32 *__restrict__ start, u32 R,
+                                                              const int *__restrict__ rank, const u32 *__restrict__ first, u32 *__restrict__ out) {
+  const u64 r64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (r64 >= R) { return; }
+  const u32 r = u32(r64);
+  if (rank[r + 1u] == rank[r]) { return; }
+  const u32 e = wide_parent_of(start, F, r);
+  const u32 open = frontier[e], j = u32(rank[r]) - u32(rank[start[e]]);
+  u32 at = j;
+  if (u32(tape[open] >> 56) == '{') {
+    if ((j & 1u) == 0) { return; }
+    at = j / 2u;
+  }
+  if (first[e] + at < first[e + 1u]) { out[first[e] + at] = open + 1u + (r - start[e]); }
+}
+// the cells of one path: its matches are one ascending list, the cell of document d the slice of the indices in [tape_begin[d], tape_begin[d + 1]).
+// offsets_row[d] = running + the matches in front of document d; with_total: offsets_row[docs] = running + count (the last path's: the column's total)
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_offsets(const doc_span_dev *__restrict__ table, u32 docs, const u32 *__restrict__ list, u32 count, u32 running,
+                                                              u32 with_total, u32 *__restrict__ offsets_row) {
+  const u64 d64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (d64 > docs || (d64 == docs && !with_total)) { return; }
+  u32 lo = 0, hi = count; // the first match at or behind tape_begin[d]
+  if (d64 < docs) {
+    const u32 begin = table[d64].tape_begin;
+    while (lo < hi) {
+      const u32 mid = lo + (hi - lo) / 2u;
+      if (list[mid] < begin) { lo = mid + 1u; } else { hi = mid; }
+    }
+  }
+  offsets_row[d64] = running + hi;
+}
+// one lane per match: value / tag begin at the path's first match
+__global__ __launch_bounds__(QUERY_THREADS) void k_wide_emit(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table, u32 docs,
+                                                           const u32 *__restrict__ list, u32 count, u64 *__restrict__ value, u8 *__restrict__ tag) {
+  const u64 j = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (j >= count) { return; }
+  const u64 cur = list[j], w = tape[cur];
+  const u32 d = wide_doc_of(table, docs, u32(cur));
+  const uint4 a = *reinterpret_cast<const uint4 *>(table + d), b = *reinterpret_cast<const uint4 *>(table + d + 1u);
+  tag[j] = u8(w >> 56);
+  value[j] = cell_value(tape, sbuf, cur, w, a.z, b.z, a.w, b.w);
+}
+
 static inline u32 blocks_of(u64 n, u32 per) { return u32((n + per - 1) / per); }
 
 } // namespace
@@ -477,5 +776,174 @@ void launch_paths_fill(const uint64_t *tape, const uint8_t *string_buf, const do
   hipLaunchKernelGGL(k_at_paths<true>, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, docs, program, levels_at, tokens_at, keys_at, row_blocks,
                      const_cast<u32 *>(offsets), static_cast<u8 *>(nullptr), static_cast<u64 *>(nullptr), value, tag);
 }
+
+// ---- the wide call's level loop ---------------------------------------------------------------------------------------------------------------------
+namespace {
+// [ctrl, 256 bytes][head: 1 byte per word][depth: 4][two frontiers: 4 + 4][extents, child flags / ranks, counts: 4 + 4 + 4 per entry][the annotation's
+// workgroup marks][the roots: 4 per document][the scans' block sums]; entries: the larger of tape_words and docs, plus 1
+struct wide_workspace {
+  u32 *ctrl;
+  u8 *head;
+  int *depth;
+  u32 *frontier[2];
+  int *ext, *rank, *count;
+  u32 *share, *roots;
+  int *partial;
+  size_t bytes;
+};
+wide_workspace carve_wide_workspace(void *base, uint32_t docs, uint64_t tape_words) {
+  const size_t entries = size_t(tape_words > docs ? tape_words : docs) + 1;
+  const uintptr_t p = reinterpret_cast<uintptr_t>(base); // (null when only the size is asked for)
+  size_t at = 0;
+  auto take = [&](size_t n) {
+    uint8_t *q = reinterpret_cast<uint8_t *>(p + at);
+    at += (n + 255) & ~size_t(255);
+    return q;
+  };
+  wide_workspace w;
+  w.ctrl = reinterpret_cast<u32 *>(take(256));
+  w.head = take(size_t(tape_words));
+  w.depth = reinterpret_cast<int *>(take(size_t(tape_words) * 4));
+  w.frontier[0] = reinterpret_cast<u32 *>(take(size_t(tape_words) * 4));
+  w.frontier[1] = reinterpret_cast<u32 *>(take(size_t(tape_words) * 4));
+  w.ext = reinterpret_cast<int *>(take(entries * 4));
+  w.rank = reinterpret_cast<int *>(take(entries * 4));
+  w.count = reinterpret_cast<int *>(take(entries * 4));
+  w.share = reinterpret_cast<u32 *>(take(size_t(blocks_of(tape_words, WIDE_SHARE)) * 4));
+  w.roots = reinterpret_cast<u32 *>(take(size_t(docs) * 4));
+  w.partial = reinterpret_cast<int *>(take((size_t(blocks_of(entries, 4096)) + 64) * 4));
+  w.bytes = at;
+  return w;
+}
+} // namespace
+
+size_t paths_wide_workspace_bytes(uint32_t K, uint32_t docs, uint64_t tape_words) {
+  (void)K; // the paths run one behind the other in the same blocks
+  return carve_wide_workspace(nullptr, docs, tape_words).bytes;
+}
+
+#define WIDE_TRY(call)                     \
+  do {                                     \
+    const hipError_t e_ = (call);          \
+    if (e_ != hipSuccess) { return e_; }   \
+  } while (0)
+
+hipError_t launch_paths_wide(const uint64_t *tape, uint64_t tape_words, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program,
+                             const uint8_t *program_host, uint32_t levels_at, uint32_t tokens_at, uint32_t keys_at, uint32_t K, uint32_t *offsets, uint8_t *status,
+                             uint64_t *value, uint8_t *tag, uint64_t match_cap, void *workspace, uint32_t *readback, hipStream_t s, uint64_t *matches_out) {
+  const wide_workspace W = carve_wide_workspace(workspace, docs, tape_words);
+  const u32 n = u32(tape_words);
+  const path_header *heads = reinterpret_cast<const path_header *>(program_host);
+  const path_level *levels = reinterpret_cast<const path_level *>(program_host + levels_at);
+  const dim3 T(QUERY_THREADS);
+  // a frontier's size, a range space's size: four bytes the host waits for
+  auto read_back = [&](const void *dev, u32 *out) -> hipError_t {
+    WIDE_TRY(hipGetLastError());
+    WIDE_TRY(hipMemcpyAsync(readback, dev, sizeof(u32), hipMemcpyDeviceToHost, s));
+    WIDE_TRY(hipStreamSynchronize(s));
+    *out = *readback;
+    return hipSuccess;
+  };
+  auto scan = [&](int *a, u32 entries) { enqueue_scan(a, entries, W.ctrl, W.partial, s); }; // (the kernel in front of it left `entries` in ctrl[0])
+  // the annotation, once for all paths
+  if (n) {
+    const u32 shares = blocks_of(n, WIDE_SHARE);
+    hipLaunchKernelGGL(k_wide_ann_summary, dim3(shares), T, 0, s, tape, n, W.share);
+    hipLaunchKernelGGL(k_wide_ann_carry, dim3(1), T, 0, s, W.share, shares);
+    hipLaunchKernelGGL(k_wide_annotate, dim3(shares), T, 0, s, tape, n, W.share, W.head, W.depth, W.ctrl);
+    scan(W.depth, n);
+  }
+  // the starting frontier, the same for every path
+  u32 n_roots = 0;
+  hipLaunchKernelGGL(k_wide_roots, dim3(blocks_of(u64(docs) + 1, QUERY_THREADS)), T, 0, s, tape, table, docs, reinterpret_cast<u32 *>(W.count), W.rank, W.ctrl);
+  scan(W.rank, docs + 1u);
+  hipLaunchKernelGGL(k_wide_compact, dim3(blocks_of(docs, QUERY_THREADS)), T, 0, s, reinterpret_cast<const u32 *>(W.count), W.rank, docs, W.roots);
+  WIDE_TRY(read_back(W.rank + docs, &n_roots));
+
+  // the levels of path k over all documents -> its matches, an ascending list in one of the frontier blocks.  first_run: the run that leaves the statuses
+  auto run_levels = [&](u32 k, bool first_run, const u32 **list, u32 *count) -> hipError_t {
+    const path_header &ph = heads[k];
+    const u32 *cur = W.roots;
+    u32 F = n_roots, flip = 0;
+    *list = cur;
+    *count = 0;
+    for (u32 L = 0; L < ph.levels && F; L++) {
+      const path_level &lv = levels[ph.first_level + L];
+      u8 *status_row = first_run && L == 0 ? status + size_t(k) * docs : nullptr;
+      u32 *out = W.frontier[flip];
+      u32 next = 0;
+      if (lv.kind == PATH_PTR || lv.kind == PATH_TAIL) {
+        hipLaunchKernelGGL(k_wide_walk, dim3(blocks_of(u64(F) + 1, QUERY_THREADS)), T, 0, s, tape, string_buf, table, docs, program, tokens_at, keys_at, k, lv.first_token, lv.tokens,
+                           cur, F, lv.kind == PATH_TAIL ? status_row : static_cast<u8 *>(nullptr), reinterpret_cast<u32 *>(W.count), W.rank, W.ctrl);
+        scan(W.rank, F + 1u);
+        hipLaunchKernelGGL(k_wide_compact, dim3(blocks_of(F, QUERY_THREADS)), T, 0, s, reinterpret_cast<const u32 *>(W.count), W.rank, F, out);
+        WIDE_TRY(read_back(W.rank + F, &next));
+      } else if (lv.kind == PATH_WILD || lv.kind == PATH_WILD_LAST) {
+        u32 R = 0;
+        const u32 *start = reinterpret_cast<const u32 *>(W.ext);
+        hipLaunchKernelGGL(k_wide_extents, dim3(blocks_of(u64(F) + 1, QUERY_THREADS)), T, 0, s, tape, table, docs, cur, F, W.ext, W.ctrl);
+        scan(W.ext, F + 1u);
+        WIDE_TRY(read_back(W.ext + F, &R));
+        if (R) {
+          hipLaunchKernelGGL(k_wide_children, dim3(blocks_of(u64(R) + 1, QUERY_THREADS)), T, 0, s, cur, F, start, R, W.head, W.depth, W.rank, W.ctrl);
+          scan(W.rank, R + 1u);
+          hipLaunchKernelGGL(k_wide_counts, dim3(blocks_of(u64(F) + 1, QUERY_THREADS)), T, 0, s, tape, cur, F, start, W.rank, W.count, W.ctrl);
+          scan(W.count, F + 1u);
+          WIDE_TRY(read_back(W.count + F, &next));
+          if (next) {
+            hipLaunchKernelGGL(k_wide_scatter, dim3(blocks_of(R, QUERY_THREADS)), T, 0, s, tape, cur, F, start, R, W.rank, reinterpret_cast<const u32 *>(W.count), out);
+          }
+        }
+      } else {
+        if (status_row) { hipLaunchKernelGGL(k_wide_status, dim3(blocks_of(F, QUERY_THREADS)), T, 0, s, table, docs, cur, F, u32(QUERY_INVALID_JSON_POINTER), status_row); }
+        return hipSuccess; // ERR22 below the root: swallowed, nothing matches
+      }
+      if (lv.kind == PATH_TAIL || lv.kind == PATH_WILD_LAST) {
+        *list = out;
+        *count = next;
+        return hipSuccess;
+      }
+      cur = out;
+      F = next;
+      flip ^= 1u;
+    }
+    return hipSuccess; // the frontier ran empty (or a program without a last level, which compile_path_program never leaves)
+  };
+
+  // first run: statuses, offsets, the total
+  std::vector<u64> first_match(K);
+  std::vector<u32> found(K);
+  const u32 *list = W.roots;
+  u64 running = 0;
+  for (u32 k = 0; k < K; k++) {
+    WIDE_TRY(hipMemsetAsync(status + size_t(k) * docs, 0, docs, s));
+    u32 count = 0;
+    WIDE_TRY(run_levels(k, true, &list, &count));
+    first_match[k] = running;
+    found[k] = count;
+    hipLaunchKernelGGL(k_wide_offsets, dim3(blocks_of(u64(docs) + 1, QUERY_THREADS)), T, 0, s, table, docs, list, count, u32(running), k + 1u == K ? 1u : 0u,
+                       offsets + size_t(k) * docs);
+    running += count;
+  }
+  *matches_out = running;
+  if (running <= 0xFFFFFFFFull && running <= match_cap) {
+    // second run, writing.  The last path's list still lies where the first run left it: it goes first, before the blocks are used again
+    for (u32 i = 0; i < K; i++) {
+      const u32 k = i == 0 ? K - 1u : i - 1u;
+      if (!found[k]) { continue; }
+      u32 count = found[k];
+      if (i) {
+        WIDE_TRY(run_levels(k, false, &list, &count));
+        count = count < found[k] ? count : found[k];
+      }
+      if (count) {
+        hipLaunchKernelGGL(k_wide_emit, dim3(blocks_of(count, QUERY_THREADS)), T, 0, s, tape, string_buf, table, docs, list, count, value + first_match[k], tag + first_match[k]);
+      }
+    }
+  }
+  WIDE_TRY(hipGetLastError());
+  return hipStreamSynchronize(s);
+}
+#undef WIDE_TRY
 
 } // namespace sjgpu
