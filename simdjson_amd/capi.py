@@ -60,6 +60,10 @@ INCORRECT_TYPE, INDEX_OUT_OF_BOUNDS, NO_SUCH_FIELD, INVALID_JSON_POINTER = 17, 1
 PATH_EXPORTS = ["sjgpu_at_paths_device", "sjgpu_at_paths_wide_device"]
 
 
+# what include/sjgpu_rows.h declares (record tables over device tapes: JSON pointers rooted at the cells of a column)
+ROWS_EXPORTS = ["sjgpu_at_pointers_from_cells_device"]
+
+
 class ScanResult(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
 
@@ -157,6 +161,8 @@ def load_library():
     L.sjgpu_at_paths_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_at_paths_wide_device.restype = ctypes.c_int
     L.sjgpu_at_paths_wide_device.argtypes = L.sjgpu_at_paths_device.argtypes
+    L.sjgpu_at_pointers_from_cells_device.restype = ctypes.c_int
+    L.sjgpu_at_pointers_from_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int
@@ -609,6 +615,74 @@ class DomParserImplementation:
             raise SjgpuError(f"sjgpu_at_paths{'_wide' if wide else ''}_device refused its arguments ({rc})")
         torch.cuda.current_stream(dev).synchronize()
         return code, docs, status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(), values[:matches].cpu().numpy().view(np.uint64)
+
+    def at_pointers_from_cells_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, root_value_ptr, root_tag_ptr, rows, pointers, value_ptr, tag_ptr,
+                                      stream=0):
+        """sjgpu_at_pointers_from_cells_device: at_pointer rooted at the `rows` cells root_value_ptr / root_tag_ptr (a row of at_pointers_device's output, the matches of
+        at_paths_device, a row of this call's own); pointers = list of bytes; value_ptr -> len(pointers) * rows uint64, tag_ptr -> as many bytes, row k = pointer k.
+        Only enqueues the walk.  -> 0 or a negative SJGPU_E_* for arguments the call refuses (raises on HIP errors and on memory the context could not get)"""
+        blob = b"".join(pointers)
+        lens = np.array([len(x) for x in pointers], dtype=np.uint32)
+        rc = self.L.sjgpu_at_pointers_from_cells_device(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs), root_value_ptr, root_tag_ptr,
+                                                        int(rows), ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(pointers),
+                                                        value_ptr, tag_ptr, stream or None)
+        if rc in (-2, -3):
+            raise SjgpuError(f"sjgpu_at_pointers_from_cells_device error {rc}: {self.last_error()}")
+        return rc
+
+    def table_many(self, data, row_path, pointers, max_depth=1024, wide=False):
+        """One row per match of row_path, one column per pointer: upload, stage 1, sjgpu_stage2_many_device, ONE sjgpu_at_paths_device call with K = 1 (wide:
+        sjgpu_at_paths_wide_device) and sjgpu_at_pointers_from_cells_device over its matches, with everything resident (the twin of extract_many and explode_many).
+        Row r of the table is match r of the path; the rows of document d are row_offsets[d] .. row_offsets[d + 1] (a document whose status is not 0 has none).
+        -> (error_code of the first broken document or 0, documents delivered, row_offsets uint32[docs + 1], tags uint8[K, rows], values uint64[K, rows])"""
+        import torch
+        a = _as_u8(data)
+        K = len(pointers)
+
+        def nothing(code, docs):
+            return code, docs, np.zeros(docs + 1, np.uint32), np.zeros((K, 0), np.uint8), np.zeros((K, 0), np.uint64)
+        if len(a) == 0:
+            return nothing(EMPTY, 0)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        buf = torch.from_numpy(np.concatenate([a, np.zeros(16, np.uint8)])).to(dev)
+        idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
+        rc = self.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, stream)
+        n, flags, _ = self.result(stream)
+        e1 = stage1_error_from_flags(n, flags)
+        if rc or e1:
+            return nothing(rc or e1, 0)
+        tape_cap = min(4 * n, len(a) + 3 * n) + 8
+        tape = torch.empty(tape_cap, dtype=torch.int64, device=dev)
+        sbuf = torch.empty(5 * (len(a) // 3) + 256, dtype=torch.uint8, device=dev)
+        table = torch.empty((n + 1) * 4, dtype=torch.int32, device=dev)
+        code, docs, tw, sb = self.stage2_many_device(buf.data_ptr(), len(a), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf.numel(), table.data_ptr(), n + 1,
+                                                     max_depth, stream)
+        if docs == 0:
+            return nothing(code, 0)
+        offsets = torch.empty(docs + 1, dtype=torch.int32, device=dev)
+        status = torch.empty(docs, dtype=torch.uint8, device=dev)
+        cap = int(tw // 8 + 1)
+        at_paths = self.at_paths_wide_device if wide else self.at_paths_device
+        for attempt in range(2):
+            root_values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            root_tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            rc, rows = at_paths(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, [row_path], offsets.data_ptr(), status.data_ptr(), root_values.data_ptr(),
+                                root_tags.data_ptr(), cap, stream)
+            if rc != -5:  # SJGPU_E_OVERFLOW: once more, with what it asks for
+                break
+            cap = rows
+        if rc:
+            raise SjgpuError(f"sjgpu_at_paths{'_wide' if wide else ''}_device refused its arguments ({rc})")
+        values = torch.empty((K, rows), dtype=torch.int64, device=dev)
+        tags = torch.empty((K, rows), dtype=torch.uint8, device=dev)
+        if K and rows:
+            rc = self.at_pointers_from_cells_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, root_values.data_ptr(), root_tags.data_ptr(), rows, pointers,
+                                                    values.data_ptr(), tags.data_ptr(), stream)
+            if rc:
+                raise SjgpuError(f"sjgpu_at_pointers_from_cells_device refused its arguments ({rc})")
+        torch.cuda.current_stream(dev).synchronize()
+        return code, docs, offsets.cpu().numpy().view(np.uint32), tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
 
     def result(self, stream=0):  # waits for `stream`
         r = ScanResult()

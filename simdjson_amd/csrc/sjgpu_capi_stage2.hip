@@ -1,9 +1,10 @@
-// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h, include/sjgpu_query.h and include/sjgpu_paths.h, what follows the structural list on the device: the strings of a
+// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h, include/sjgpu_query.h, include/sjgpu_paths.h and include/sjgpu_rows.h, what follows the structural list on the device: the strings of a
 // document, On-Demand's raw key comparison, stage 2 (the DOM tape of a document, the tapes of a document stream), sjgpu_parse and sjgpu_parse_many, and the queries over the tapes
 // (JSON pointers -> typed columns, a string column -> offsets + characters).  Shared with the other units: sjgpu_ctx.h.
 #include "sjgpu_ctx.h"
 #include "sjgpu_query.h"
 #include "sjgpu_paths.h"
+#include "sjgpu_rows.h"
 #include "sj_path_program.h"
 
 extern "C" {
@@ -349,14 +350,22 @@ int sjgpu_parse(sjgpu_ctx *ctx, const uint8_t *buf, size_t len, uint32_t max_dep
 }
 
 // ---- queries over device tapes (sjgpu_query.hip) ---------------------------------------------------------------------------------------------
-int sjgpu_at_pointers_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
-                             uint32_t docs, const uint8_t *pointers, const uint32_t *pointer_lens, uint32_t K, void *value_dev, void *tag_dev, void *stream) {
+} // extern "C"
+
+namespace {
+// What sjgpu_at_pointers_device and sjgpu_at_pointers_from_cells_device do before their walk: the argument checks they share, the pointer program, K == 0 / no lanes,
+// the wait for the context's previous walk, the context's block -- [0] the table check's word, [256] the program, [*extra_at] `extra` bytes more for the caller --, the
+// upload and the table check.  lanes: the cells of one row (documents, or root cells).  -> 0 with *done = false: the program lies at ctx->d_query + 256 and the table
+// passed; *done = true: the call is over with the code returned.
+int pointers_begin(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                   uint32_t lanes, const uint8_t *pointers, const uint32_t *pointer_lens, uint32_t K, void *value_dev, void *tag_dev, void *stream, size_t extra,
+                   query_program *prog, size_t *extra_at, hipStream_t *stream_out, bool *done) {
+  *done = true;
   if (!ctx || !tape_dev || !string_buf_dev || !docs_dev || !value_dev || !tag_dev || (K && (!pointers || !pointer_lens))) { return SJGPU_E_BADARG; }
   if ((reinterpret_cast<uintptr_t>(tape_dev) & 7u) || (reinterpret_cast<uintptr_t>(value_dev) & 7u) || (reinterpret_cast<uintptr_t>(docs_dev) & 15u)) { return SJGPU_E_BADARG; }
   if (tape_words > 0xFFFFFFFFull || string_bytes > 0xFFFFFFFFull || docs >= 0xFFFFFFF0u) { return SJGPU_E_BADARG; } // the table's words are 32 bits
-  query_program prog;
-  if (!compile_query_program(pointers, pointer_lens, K, &prog)) { return SJGPU_E_BADARG; }
-  if (K == 0 || docs == 0) { return 0; }
+  if (!compile_query_program(pointers, pointer_lens, K, prog)) { return SJGPU_E_BADARG; }
+  if (K == 0 || lanes == 0) { return 0; }
   SJ_TRY(ctx, hipSetDevice(ctx->device));
   // the blocks are the context's: the walk of the previous call must have read its pointers before they are overwritten
   if (ctx->query_in_flight) {
@@ -364,8 +373,9 @@ int sjgpu_at_pointers_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape
     ctx->query_in_flight = false;
   }
   if (!ctx->ev_query) { SJ_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_query, hipEventDisableTiming)); }
-  const size_t block = 256 + prog.bytes.size(); // [0] the table check's word, [256] the program
-  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, block);
+  const size_t block = 256 + prog->bytes.size(); // what goes up
+  *extra_at = (block + 255) & ~size_t(255);
+  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, extra ? *extra_at + extra : block);
   if (rc) { return rc; }
   if (ctx->h_query_bytes < block) {
     if (ctx->h_query) { (void)hipHostFree(ctx->h_query); ctx->h_query = nullptr; ctx->h_query_bytes = 0; }
@@ -373,18 +383,56 @@ int sjgpu_at_pointers_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape
     ctx->h_query_bytes = block;
   }
   std::memset(ctx->h_query, 0, 256);
-  std::memcpy(ctx->h_query + 256, prog.bytes.data(), prog.bytes.size());
+  std::memcpy(ctx->h_query + 256, prog->bytes.data(), prog->bytes.size());
   hipStream_t s = pick(ctx, stream);
-  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
+  *stream_out = s;
   SJ_TRY(ctx, hipMemcpyAsync(ctx->d_query, ctx->h_query, block, hipMemcpyHostToDevice, s));
-  launch_query_check_table(table, docs, tape_words, string_bytes, reinterpret_cast<uint32_t *>(ctx->d_query), s);
+  launch_query_check_table(static_cast<const doc_span_dev *>(docs_dev), docs, tape_words, string_bytes, reinterpret_cast<uint32_t *>(ctx->d_query), s);
   SJ_TRY(ctx, hipGetLastError());
   uint32_t *const bad = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192); // (the pinned block's last slot: the scan and stage 2 use [0, 192))
   SJ_TRY(ctx, hipMemcpyAsync(bad, ctx->d_query, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   SJ_TRY(ctx, hipStreamSynchronize(s));
   if (*bad) { return SJGPU_E_BADARG; }
-  launch_at_pointers(static_cast<const uint64_t *>(tape_dev), static_cast<const uint8_t *>(string_buf_dev), table, docs, ctx->d_query + 256, prog.tokens_at, prog.keys_at, K,
-                     static_cast<uint64_t *>(value_dev), static_cast<uint8_t *>(tag_dev), s);
+  *done = false;
+  return 0;
+}
+} // namespace
+
+extern "C" {
+
+int sjgpu_at_pointers_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                             uint32_t docs, const uint8_t *pointers, const uint32_t *pointer_lens, uint32_t K, void *value_dev, void *tag_dev, void *stream) {
+  query_program prog;
+  size_t extra_at = 0;
+  hipStream_t s = nullptr;
+  bool done = true;
+  const int rc = pointers_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, docs, pointers, pointer_lens, K, value_dev, tag_dev, stream, 0, &prog,
+                                &extra_at, &s, &done);
+  if (done) { return rc; }
+  launch_at_pointers(static_cast<const uint64_t *>(tape_dev), static_cast<const uint8_t *>(string_buf_dev), static_cast<const doc_span_dev *>(docs_dev), docs, ctx->d_query + 256,
+                     prog.tokens_at, prog.keys_at, K, static_cast<uint64_t *>(value_dev), static_cast<uint8_t *>(tag_dev), s);
+  SJ_TRY(ctx, hipGetLastError());
+  SJ_TRY(ctx, hipEventRecord(ctx->ev_query, s));
+  ctx->query_in_flight = true;
+  return 0;
+}
+
+// the same walk rooted at the cells of one row (include/sjgpu_rows.h).  The roots' verdicts (k_rows_locate, 4 bytes per root) lie behind the program in the
+// context's block: the event that guards the program guards them
+int sjgpu_at_pointers_from_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                                        uint32_t docs, const void *root_value_dev, const void *root_tag_dev, uint32_t rows, const uint8_t *pointers,
+                                        const uint32_t *pointer_lens, uint32_t K, void *value_dev, void *tag_dev, void *stream) {
+  if (!root_value_dev || !root_tag_dev || (reinterpret_cast<uintptr_t>(root_value_dev) & 7u) || rows >= 0xFFFFFFF0u) { return SJGPU_E_BADARG; }
+  query_program prog;
+  size_t where_at = 0;
+  hipStream_t s = nullptr;
+  bool done = true;
+  const int rc = pointers_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, rows, pointers, pointer_lens, K, value_dev, tag_dev, stream,
+                                size_t(rows) * sizeof(uint32_t), &prog, &where_at, &s, &done);
+  if (done) { return rc; }
+  launch_at_pointers_rooted(static_cast<const uint64_t *>(tape_dev), static_cast<const uint8_t *>(string_buf_dev), static_cast<const doc_span_dev *>(docs_dev), docs,
+                            static_cast<const uint64_t *>(root_value_dev), static_cast<const uint8_t *>(root_tag_dev), rows, reinterpret_cast<uint32_t *>(ctx->d_query + where_at),
+                            ctx->d_query + 256, prog.tokens_at, prog.keys_at, K, static_cast<uint64_t *>(value_dev), static_cast<uint8_t *>(tag_dev), s);
   SJ_TRY(ctx, hipGetLastError());
   SJ_TRY(ctx, hipEventRecord(ctx->ev_query, s));
   ctx->query_in_flight = true;

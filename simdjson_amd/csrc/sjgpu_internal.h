@@ -289,6 +289,11 @@ void launch_query_check_table(const doc_span_dev *table, uint32_t docs, uint64_t
 // program: what compile_query_program (sj_query_program.h) left, in device memory, 16-byte aligned; K >= 1, docs >= 1; a table that passed the check
 void launch_at_pointers(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t tokens_at,
                         uint32_t keys_at, uint32_t K, uint64_t *value, uint8_t *tag, hipStream_t s);
+// the same walk rooted at the cells of one row (include/sjgpu_rows.h): k_rows_locate settles every root once in where[0 .. rows) (device memory), k_at_pointers_rooted
+// walks the K * rows cells.  K >= 1, rows >= 1, docs >= 0; a table that passed the check
+void launch_at_pointers_rooted(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag,
+                               uint32_t rows, uint32_t *where, const uint8_t *program, uint32_t tokens_at, uint32_t keys_at, uint32_t K, uint64_t *value, uint8_t *tag,
+                               hipStream_t s);
 // offsets[0 .. docs] = exclusive sum of the string cells' lengths; -> the device address of the 64-bit total (workspace: gather_workspace_bytes(docs), 256-byte aligned)
 size_t gather_workspace_bytes(uint32_t docs);
 const void *launch_gather_offsets(const uint64_t *value, const uint8_t *tag, uint32_t docs, uint64_t string_bytes, uint32_t *offsets, void *workspace, hipStream_t s);

@@ -1,5 +1,6 @@
 // simdjson_amd/csrc/sjgpu_query.hip -- queries over device tapes: a batched dom::element::at_pointer (sjgpu_at_pointers_device) and the
-// string column as offsets + characters (sjgpu_gather_strings_device).  Contract: include/sjgpu_query.h.
+// string column as offsets + characters (sjgpu_gather_strings_device).  Contract: include/sjgpu_query.h.  The same walk rooted at the cells of a
+// column (sjgpu_at_pointers_from_cells_device, include/sjgpu_rows.h) is at the end of the kernels.
 //
 // The walk.  K pointers x docs documents = K * docs CELLS; one lane walks one cell, the lanes of a workgroup take consecutive documents of ONE
 // pointer: the column stores are coalesced, the workgroup's pointer -- its tokens as sj_query_program.h compiled them and its
@@ -125,6 +126,24 @@ __device__ __forceinline__ u64 cell_value(const u64 *__restrict__ tape, const u8
   return 0;
 }
 
+// pointer qp of the program into the workgroup's LDS, by all of its lanes: the pointer's tokens (4 words of 8 bytes each) and its key area -- what is behind
+// the last key is never compared.  Ends behind the barrier.  The prologue of k_at_pointers and of k_at_pointers_rooted.
+__device__ __forceinline__ void stage_pointer(const u8 *__restrict__ prog, u32 tokens_at, u32 keys_at, const query_pointer &qp, query_token *s_tok /* LDS */, u64 *s_key /* LDS */) {
+  const u64 *src = reinterpret_cast<const u64 *>(prog + tokens_at) + u64(qp.first_token) * (sizeof(query_token) / 8);
+  u64 *dst = reinterpret_cast<u64 *>(s_tok);
+  for (u32 j = threadIdx.x; j < qp.tokens * u32(sizeof(query_token) / 8); j += QUERY_THREADS) { dst[j] = src[j]; }
+  u32 key_words = 0;
+  if (qp.tokens) {
+    const query_token last = reinterpret_cast<const query_token *>(prog + tokens_at)[qp.first_token + qp.tokens - 1u];
+    key_words = (last.key_off + last.key_len + 7u) / 8u;
+  }
+  key_words = key_words < QUERY_KEY_AREA / 8 ? key_words : QUERY_KEY_AREA / 8;
+  const u64 *ksrc = reinterpret_cast<const u64 *>(prog + keys_at + qp.keys_at);
+  for (u32 j = threadIdx.x; j < key_words; j += QUERY_THREADS) { s_key[j] = ksrc[j]; }
+  lds_writes_done();
+  __syncthreads();
+}
+
 // grid: K rows of row_blocks workgroups, row k = pointer k (one dimension: at most 64 * 2^24 workgroups)
 __global__ __launch_bounds__(QUERY_THREADS) void k_at_pointers(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table, u32 docs,
                                                              const u8 *__restrict__ prog, u32 tokens_at, u32 keys_at, u32 row_blocks, u64 *__restrict__ value, u8 *__restrict__ tag) {
@@ -132,22 +151,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_pointers(const u64 *__rest
   __shared__ u64 s_key[QUERY_KEY_AREA / 8];
   const u32 k = blockIdx.x / row_blocks, row_block = blockIdx.x - k * row_blocks;
   const query_pointer qp = reinterpret_cast<const query_pointer *>(prog)[k];
-  {
-    // the pointer's tokens (4 words of 8 bytes each) and its key area: what is behind the last key is never compared
-    const u64 *src = reinterpret_cast<const u64 *>(prog + tokens_at) + u64(qp.first_token) * (sizeof(query_token) / 8);
-    u64 *dst = reinterpret_cast<u64 *>(s_tok);
-    for (u32 j = threadIdx.x; j < qp.tokens * u32(sizeof(query_token) / 8); j += QUERY_THREADS) { dst[j] = src[j]; }
-    u32 key_words = 0;
-    if (qp.tokens) {
-      const query_token last = reinterpret_cast<const query_token *>(prog + tokens_at)[qp.first_token + qp.tokens - 1u];
-      key_words = (last.key_off + last.key_len + 7u) / 8u;
-    }
-    key_words = key_words < QUERY_KEY_AREA / 8 ? key_words : QUERY_KEY_AREA / 8;
-    const u64 *ksrc = reinterpret_cast<const u64 *>(prog + keys_at + qp.keys_at);
-    for (u32 j = threadIdx.x; j < key_words; j += QUERY_THREADS) { s_key[j] = ksrc[j]; }
-  }
-  lds_writes_done();
-  __syncthreads();
+  stage_pointer(prog, tokens_at, keys_at, qp, s_tok, s_key);
   const u64 d64 = u64(row_block) * QUERY_THREADS + threadIdx.x;
   if (d64 >= docs) { return; }
   const u32 d = u32(d64);
@@ -717,6 +721,94 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_wide_emit(const u64 *__restri
   value[j] = cell_value(tape, sbuf, cur, w, a.z, b.z, a.w, b.w);
 }
 
+// ---- the rows (include/sjgpu_rows.h: sjgpu_at_pointers_from_cells_device) ---------------------------------------------------------------------------
+// at_pointer of K pointers rooted at the CELLS of one row: K x rows cells, one lane each, mapped like k_at_pointers.  What a root is -- its document, or
+// that no walk is needed -- does not depend on the pointer, so it is settled once per root by k_rows_locate and left in 4 bytes:
+//   below ROWS_SPECIAL           the document d of a container root whose cell agrees with the tape
+//   ROWS_SPECIAL                 a scalar root: the empty pointer copies the cell, any other gets the scalar's verdict from the program
+//   ROWS_SPECIAL | (code - 16)   every pointer answers `code` (a failed root keeps its 17 / 19 / 20 / 22; a tag that is none, or a container cell that disagrees
+//                                with the tape, is NO_SUCH_FIELD)
+// (docs is below 0xFFFFFFF0: the C-ABI refuses more.)
+constexpr u32 ROWS_SPECIAL = 0xFFFFFFF0u;
+
+__device__ __forceinline__ bool is_query_code(u32 t) {
+  return t == QUERY_INCORRECT_TYPE || t == QUERY_INDEX_OUT_OF_BOUNDS || t == QUERY_NO_SUCH_FIELD || t == QUERY_INVALID_JSON_POINTER;
+}
+
+// one lane per root.  A container cell is followed only when its opening index c lies INSIDE a document (behind its root word), the word there carries the
+// cell's tag and points where the cell's high half says: log2(docs) table reads, one tape word.
+__global__ __launch_bounds__(QUERY_THREADS) void k_rows_locate(const u64 *__restrict__ tape, const doc_span_dev *__restrict__ table, u32 docs, const u64 *__restrict__ root_value,
+                                                             const u8 *__restrict__ root_tag, u32 rows, u32 *__restrict__ where) {
+  const u64 r64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (r64 >= rows) { return; }
+  const u32 t = root_tag[r64];
+  u32 out = ROWS_SPECIAL | (QUERY_NO_SUCH_FIELD - 16u);
+  if (is_container_tag(t)) {
+    const u64 v = root_value[r64];
+    const u32 c = u32(v & LOW32);
+    if (docs && c > table[0].tape_begin) {
+      const u32 d = wide_doc_of(table, docs, c);
+      const u64 base = table[d].tape_begin, doc_end = table[d + 1u].tape_begin;
+      if (c > base && c < doc_end) { // (at or behind the last entry: outside every document)
+        const u64 w = tape[c];
+        if (u32(w >> 56) == t && base + (w & LOW32) == (v >> 32)) { out = d; }
+      }
+    }
+  } else if (t == '"' || is_number_tag(t) || t == 't' || t == 'f' || t == 'n') {
+    out = ROWS_SPECIAL;
+  } else if (is_query_code(t)) {
+    out = ROWS_SPECIAL | (t - 16u);
+  }
+  where[r64] = out;
+}
+
+// grid: K rows of row_blocks workgroups, row k = pointer k; lane = root
+__global__ __launch_bounds__(QUERY_THREADS) void k_at_pointers_rooted(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table,
+                                                                    const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where, u32 rows,
+                                                                    const u8 *__restrict__ prog, u32 tokens_at, u32 keys_at, u32 row_blocks, u64 *__restrict__ value,
+                                                                    u8 *__restrict__ tag) {
+  __shared__ query_token s_tok[QUERY_MAX_TOKENS];
+  __shared__ u64 s_key[QUERY_KEY_AREA / 8];
+  const u32 k = blockIdx.x / row_blocks, row_block = blockIdx.x - k * row_blocks;
+  const query_pointer qp = reinterpret_cast<const query_pointer *>(prog)[k];
+  stage_pointer(prog, tokens_at, keys_at, qp, s_tok, s_key);
+  const u64 r64 = u64(row_block) * QUERY_THREADS + threadIdx.x;
+  if (r64 >= rows) { return; }
+  const u32 m = where[r64];
+  u32 out_tag;
+  u64 out_value = 0;
+  if (m > ROWS_SPECIAL) {
+    out_tag = (m & 15u) + 16u;
+  } else if (m == ROWS_SPECIAL) {
+    if (qp.code) {
+      out_tag = qp.code;
+    } else if (qp.tokens) {
+      out_tag = s_tok[0].scalar_code;
+    } else {
+      out_tag = root_tag[r64];
+      out_value = root_value[r64];
+    }
+  } else {
+    const uint4 a = *reinterpret_cast<const uint4 *>(table + m), b = *reinterpret_cast<const uint4 *>(table + m + 1u);
+    const u64 base = a.z, doc_end = b.z;
+    const u64 str_base = a.w, str_end = b.w;
+    u32 code = qp.code;
+    if (!code) {
+      const u64 v = root_value[r64];
+      u64 cur = v & LOW32, w = tape[cur]; // (k_rows_locate found cur inside the document, and w to agree with the cell)
+      const u64 limit = (v >> 32) < doc_end ? (v >> 32) : doc_end;
+      code = walk_tokens(tape, sbuf, s_tok, qp.tokens, reinterpret_cast<const u8 *>(s_key), base, limit, str_base, str_end, cur, w);
+      if (!code) { out_value = cell_value(tape, sbuf, cur, w, base, doc_end, str_base, str_end); }
+      out_tag = code ? code : u32(w >> 56);
+    } else {
+      out_tag = code;
+    }
+  }
+  const u64 cell = u64(k) * rows + r64;
+  tag[cell] = u8(out_tag);
+  value[cell] = out_value;
+}
+
 static inline u32 blocks_of(u64 n, u32 per) { return u32((n + per - 1) / per); }
 
 } // namespace
@@ -729,6 +821,15 @@ void launch_at_pointers(const uint64_t *tape, const uint8_t *string_buf, const d
                         uint32_t keys_at, uint32_t K, uint64_t *value, uint8_t *tag, hipStream_t s) {
   const u32 row_blocks = blocks_of(docs, QUERY_THREADS);
   hipLaunchKernelGGL(k_at_pointers, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, docs, program, tokens_at, keys_at, row_blocks, value, tag);
+}
+
+void launch_at_pointers_rooted(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag,
+                               uint32_t rows, uint32_t *where, const uint8_t *program, uint32_t tokens_at, uint32_t keys_at, uint32_t K, uint64_t *value, uint8_t *tag,
+                               hipStream_t s) {
+  const u32 row_blocks = blocks_of(rows, QUERY_THREADS);
+  hipLaunchKernelGGL(k_rows_locate, dim3(row_blocks), dim3(QUERY_THREADS), 0, s, tape, table, docs, root_value, root_tag, rows, where);
+  hipLaunchKernelGGL(k_at_pointers_rooted, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, root_value, root_tag, where, rows, program, tokens_at, keys_at,
+                     row_blocks, value, tag);
 }
 
 // [ctrl, 256 bytes][the blocks' sums][the scan's block sums]
