@@ -64,6 +64,10 @@ PATH_EXPORTS = ["sjgpu_at_paths_device", "sjgpu_at_paths_wide_device"]
 ROWS_EXPORTS = ["sjgpu_at_pointers_from_cells_device"]
 
 
+# what include/sjgpu_lists.h declares (list columns over device tapes: JSONPaths with wildcards rooted at the cells of a column)
+LISTS_EXPORTS = ["sjgpu_at_paths_from_cells_device"]
+
+
 class ScanResult(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
 
@@ -163,6 +167,9 @@ def load_library():
     L.sjgpu_at_paths_wide_device.argtypes = L.sjgpu_at_paths_device.argtypes
     L.sjgpu_at_pointers_from_cells_device.restype = ctypes.c_int
     L.sjgpu_at_pointers_from_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
+    L.sjgpu_at_paths_from_cells_device.restype = ctypes.c_int
+    L.sjgpu_at_paths_from_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp,
+                                                   ctypes.c_uint64, vp, u64p]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int
@@ -558,11 +565,13 @@ class DomParserImplementation:
         return self._at_paths("sjgpu_at_paths_wide_device", tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr,
                               match_cap, stream)
 
-    def _at_paths(self, name, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap, stream):
+    def _at_paths(self, name, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap, stream, roots=()):
+        """roots: (root_value_ptr, root_tag_ptr, rows) for the call rooted at cells, which takes them behind docs"""
         blob = b"".join(paths)
         lens = np.array([len(x) for x in paths], dtype=np.uint32)
         matches = ctypes.c_uint64(0)
-        rc = getattr(self.L, name)(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs),
+        roots = (roots[0] or None, roots[1] or None, int(roots[2])) if roots else ()
+        rc = getattr(self.L, name)(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs), *roots,
                                    ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(paths), offsets_ptr, status_ptr or None,
                                    value_ptr or None, tag_ptr or None, int(match_cap), stream or None, ctypes.byref(matches))
         if rc in (-2, -3):
@@ -683,6 +692,77 @@ class DomParserImplementation:
                 raise SjgpuError(f"sjgpu_at_pointers_from_cells_device refused its arguments ({rc})")
         torch.cuda.current_stream(dev).synchronize()
         return code, docs, offsets.cpu().numpy().view(np.uint32), tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
+
+    def at_paths_from_cells_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, root_value_ptr, root_tag_ptr, rows, paths, offsets_ptr, status_ptr,
+                                   value_ptr, tag_ptr, match_cap, stream=0):
+        """sjgpu_at_paths_from_cells_device: at_path_with_wildcard rooted at the `rows` cells root_value_ptr / root_tag_ptr (as for at_pointers_from_cells_device); paths = list
+        of bytes; offsets_ptr -> len(paths) * rows + 1 uint32, status_ptr -> len(paths) * rows bytes, value_ptr / tag_ptr -> match_cap uint64 / bytes.
+        -> (code, matches): 0, CAPACITY or a negative SJGPU_E_* (raises on HIP errors and on memory the context could not get)"""
+        return self._at_paths("sjgpu_at_paths_from_cells_device", tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr,
+                              match_cap, stream, (root_value_ptr, root_tag_ptr, rows))
+
+    def lists_many(self, data, row_path, paths, max_depth=1024, wide=False, first_cap=None):
+        """One row per match of row_path, one LIST column per path: upload, stage 1, sjgpu_stage2_many_device, ONE sjgpu_at_paths_device call with K = 1 (wide:
+        sjgpu_at_paths_wide_device) and sjgpu_at_paths_from_cells_device over its matches, with everything resident (the twin of table_many).  The new call is repeated once
+        with the capacity it reported (first_cap: its first guess, by default one match per tape word in eight).  Row r is match r of row_path; the rows of document d
+        are row_offsets[d] .. row_offsets[d + 1]; the list of row r under path k is tags / values[offsets[k * rows + r] .. offsets[k * rows + r + 1]).
+        -> (error_code of the first broken document or 0, documents delivered, row_offsets uint32[docs + 1], status uint8[K, rows], offsets uint32[K * rows + 1],
+        tags uint8[matches], values uint64[matches])"""
+        import torch
+        a = _as_u8(data)
+        K = len(paths)
+
+        def nothing(code, docs):
+            return code, docs, np.zeros(docs + 1, np.uint32), np.zeros((K, 0), np.uint8), np.zeros(1, np.uint32), np.zeros(0, np.uint8), np.zeros(0, np.uint64)
+        if len(a) == 0:
+            return nothing(EMPTY, 0)
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        buf = torch.from_numpy(np.concatenate([a, np.zeros(16, np.uint8)])).to(dev)
+        idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
+        rc = self.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, stream)
+        n, flags, _ = self.result(stream)
+        e1 = stage1_error_from_flags(n, flags)
+        if rc or e1:
+            return nothing(rc or e1, 0)
+        tape_cap = min(4 * n, len(a) + 3 * n) + 8
+        tape = torch.empty(tape_cap, dtype=torch.int64, device=dev)
+        sbuf = torch.empty(5 * (len(a) // 3) + 256, dtype=torch.uint8, device=dev)
+        table = torch.empty((n + 1) * 4, dtype=torch.int32, device=dev)
+        code, docs, tw, sb = self.stage2_many_device(buf.data_ptr(), len(a), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf.numel(), table.data_ptr(), n + 1,
+                                                     max_depth, stream)
+        if docs == 0:
+            return nothing(code, 0)
+        row_offsets = torch.empty(docs + 1, dtype=torch.int32, device=dev)
+        row_status = torch.empty(docs, dtype=torch.uint8, device=dev)
+        cap = int(tw // 8 + 1)
+        at_paths = self.at_paths_wide_device if wide else self.at_paths_device
+        for attempt in range(2):
+            root_values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            root_tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            rc, rows = at_paths(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, [row_path], row_offsets.data_ptr(), row_status.data_ptr(), root_values.data_ptr(),
+                                root_tags.data_ptr(), cap, stream)
+            if rc != -5:  # SJGPU_E_OVERFLOW: once more, with what it asks for
+                break
+            cap = rows
+        if rc:
+            raise SjgpuError(f"sjgpu_at_paths{'_wide' if wide else ''}_device refused its arguments ({rc})")
+        offsets = torch.empty(K * rows + 1, dtype=torch.int32, device=dev)
+        status = torch.empty((K, rows), dtype=torch.uint8, device=dev)
+        cap = int(tw // 8 + 1 if first_cap is None else first_cap)
+        for attempt in range(2):
+            values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            rc, matches = self.at_paths_from_cells_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, root_values.data_ptr(), root_tags.data_ptr(), rows, paths,
+                                                          offsets.data_ptr(), status.data_ptr(), values.data_ptr(), tags.data_ptr(), cap, stream)
+            if rc != -5:
+                break
+            cap = matches
+        if rc:
+            raise SjgpuError(f"sjgpu_at_paths_from_cells_device refused its arguments ({rc})")
+        torch.cuda.current_stream(dev).synchronize()
+        return (code, docs, row_offsets.cpu().numpy().view(np.uint32), status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(),
+                values[:matches].cpu().numpy().view(np.uint64))
 
     def result(self, stream=0):  # waits for `stream`
         r = ScanResult()

@@ -1,10 +1,11 @@
-// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h, include/sjgpu_query.h, include/sjgpu_paths.h and include/sjgpu_rows.h, what follows the structural list on the device: the strings of a
+// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h, include/sjgpu_query.h, include/sjgpu_paths.h, include/sjgpu_rows.h and include/sjgpu_lists.h, what follows the structural list on the device: the strings of a
 // document, On-Demand's raw key comparison, stage 2 (the DOM tape of a document, the tapes of a document stream), sjgpu_parse and sjgpu_parse_many, and the queries over the tapes
 // (JSON pointers -> typed columns, a string column -> offsets + characters).  Shared with the other units: sjgpu_ctx.h.
 #include "sjgpu_ctx.h"
 #include "sjgpu_query.h"
 #include "sjgpu_paths.h"
 #include "sjgpu_rows.h"
+#include "sjgpu_lists.h"
 #include "sj_path_program.h"
 
 extern "C" {
@@ -469,15 +470,16 @@ int sjgpu_gather_strings_device(sjgpu_ctx *ctx, const void *string_buf_dev, uint
 } // extern "C"
 
 namespace {
-// What sjgpu_at_paths_device and sjgpu_at_paths_wide_device do before their first kernel: the argument checks, the level program, K == 0 / docs == 0, the
-// context's program block and the road's workspace in d_tmp (wide: paths_wide_workspace_bytes, else paths_workspace_bytes), the upload and the table check.  -> 0 with *done = false: the program lies at ctx->d_query + 256 and the
-// table passed; *done = true: the call is over with the code returned.
+// What sjgpu_at_paths_device, sjgpu_at_paths_wide_device and sjgpu_at_paths_from_cells_device do before their first kernel: the argument checks they share, the level
+// program, K == 0 / no lanes, the context's block -- [0] the table check's word, [256] the program, [*extra_at] `extra` bytes more for the caller -- and the road's
+// workspace in d_tmp (wide: paths_wide_workspace_bytes, else paths_workspace_bytes), the upload and the table check.  lanes: the cells of one path (documents, or root
+// cells).  -> 0 with *done = false: the program lies at ctx->d_query + 256 and the table passed; *done = true: the call is over with the code returned.
 int paths_begin(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
-                const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev, uint64_t match_cap, void *stream,
-                uint64_t *matches_out, bool wide, path_program *prog, hipStream_t *stream_out, bool *done) {
+                uint32_t lanes, const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev, uint64_t match_cap,
+                void *stream, uint64_t *matches_out, bool wide, size_t extra, path_program *prog, size_t *extra_at, hipStream_t *stream_out, bool *done) {
   *done = true;
   if (matches_out) { *matches_out = 0; }
-  if (!ctx || !tape_dev || !string_buf_dev || !docs_dev || !offsets_dev || !matches_out || (K && (!paths || !path_lens)) || (K && docs && !status_dev) ||
+  if (!ctx || !tape_dev || !string_buf_dev || !docs_dev || !offsets_dev || !matches_out || (K && (!paths || !path_lens)) || (K && lanes && !status_dev) ||
       (match_cap && (!value_dev || !tag_dev))) {
     return SJGPU_E_BADARG;
   }
@@ -485,13 +487,13 @@ int paths_begin(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const
       (reinterpret_cast<uintptr_t>(offsets_dev) & 3u)) {
     return SJGPU_E_BADARG;
   }
-  if (tape_words > 0xFFFFFFFFull || string_bytes > 0xFFFFFFFFull || docs >= 0xFFFFFFF0u) { return SJGPU_E_BADARG; } // the table's words are 32 bits
+  if (tape_words > 0xFFFFFFFFull || string_bytes > 0xFFFFFFFFull || docs >= 0xFFFFFFF0u || lanes >= 0xFFFFFFF0u) { return SJGPU_E_BADARG; } // the table's words are 32 bits
   if (!compile_path_program(paths, path_lens, K, prog)) { return SJGPU_E_BADARG; }
-  if (uint64_t(K) * docs + 1 > 0xFFFFFFF0ull) { return SJGPU_E_BADARG; } // the scan's entries are indexed by 32-bit words
+  if (uint64_t(K) * lanes + 1 > 0xFFFFFFF0ull) { return SJGPU_E_BADARG; } // the scan's entries are indexed by 32-bit words
   SJ_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = pick(ctx, stream);
   *stream_out = s;
-  if (K == 0 || docs == 0) {
+  if (K == 0 || lanes == 0) {
     SJ_TRY(ctx, hipMemsetAsync(offsets_dev, 0, sizeof(uint32_t), s));
     SJ_TRY(ctx, hipStreamSynchronize(s));
     return 0;
@@ -502,9 +504,10 @@ int paths_begin(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const
     ctx->query_in_flight = false;
   }
   const size_t block = 256 + prog->bytes.size(); // [0] the table check's word, [256] the program
-  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, block);
+  *extra_at = (block + 255) & ~size_t(255);
+  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, extra ? *extra_at + extra : block);
   if (rc) { return rc; }
-  rc = ensure_tmp(ctx, wide ? paths_wide_workspace_bytes(K, docs, tape_words) : paths_workspace_bytes(K, docs));
+  rc = ensure_tmp(ctx, wide ? paths_wide_workspace_bytes(K, docs, tape_words) : paths_workspace_bytes(K, lanes));
   if (rc) { return rc; }
   if (ctx->h_query_bytes < block) {
     if (ctx->h_query) { (void)hipHostFree(ctx->h_query); ctx->h_query = nullptr; ctx->h_query_bytes = 0; }
@@ -531,10 +534,11 @@ int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_wo
                           const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev, uint64_t match_cap,
                           void *stream, uint64_t *matches_out) {
   path_program prog;
+  size_t extra_at = 0;
   hipStream_t s = nullptr;
   bool done = true;
-  const int rc = paths_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, paths, path_lens, K, offsets_dev, status_dev, value_dev, tag_dev, match_cap,
-                             stream, matches_out, false, &prog, &s, &done);
+  const int rc = paths_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, docs, paths, path_lens, K, offsets_dev, status_dev, value_dev, tag_dev,
+                             match_cap, stream, matches_out, false, 0, &prog, &extra_at, &s, &done);
   if (done) { return rc; }
   uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
   const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
@@ -564,10 +568,11 @@ int sjgpu_at_paths_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t ta
                                const uint8_t *paths, const uint32_t *path_lens, uint32_t K, void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev,
                                uint64_t match_cap, void *stream, uint64_t *matches_out) {
   path_program prog;
+  size_t extra_at = 0;
   hipStream_t s = nullptr;
   bool done = true;
-  const int rc = paths_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, paths, path_lens, K, offsets_dev, status_dev, value_dev, tag_dev, match_cap,
-                             stream, matches_out, true, &prog, &s, &done);
+  const int rc = paths_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, docs, paths, path_lens, K, offsets_dev, status_dev, value_dev, tag_dev,
+                             match_cap, stream, matches_out, true, 0, &prog, &extra_at, &s, &done);
   if (done) { return rc; }
   uint32_t *const readback = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
   uint64_t matches = 0;
@@ -577,6 +582,45 @@ int sjgpu_at_paths_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t ta
   *matches_out = matches;
   if (matches > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
   if (matches > match_cap) { return SJGPU_E_OVERFLOW; }
+  return 0;
+}
+
+// the depth-first walk rooted at the cells of one row (include/sjgpu_lists.h).  The roots' verdicts (k_rows_locate, 4 bytes per root) lie behind the program in the
+// context's block, made once in front of the count and read by both passes of all K paths
+int sjgpu_at_paths_from_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                                     uint32_t docs, const void *root_value_dev, const void *root_tag_dev, uint32_t rows, const uint8_t *paths, const uint32_t *path_lens, uint32_t K,
+                                     void *offsets_dev, void *status_dev, void *value_dev, void *tag_dev, uint64_t match_cap, void *stream, uint64_t *matches_out) {
+  if (matches_out) { *matches_out = 0; }
+  if ((rows && (!root_value_dev || !root_tag_dev)) || (reinterpret_cast<uintptr_t>(root_value_dev) & 7u)) { return SJGPU_E_BADARG; }
+  path_program prog;
+  size_t where_at = 0;
+  hipStream_t s = nullptr;
+  bool done = true;
+  const int rc = paths_begin(ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, rows, paths, path_lens, K, offsets_dev, status_dev, value_dev, tag_dev,
+                             match_cap, stream, matches_out, false, size_t(rows) * sizeof(uint32_t), &prog, &where_at, &s, &done);
+  if (done) { return rc; }
+  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
+  const uint64_t *tape = static_cast<const uint64_t *>(tape_dev);
+  const uint8_t *sbuf = static_cast<const uint8_t *>(string_buf_dev);
+  const uint64_t *root_value = static_cast<const uint64_t *>(root_value_dev);
+  uint32_t *where = reinterpret_cast<uint32_t *>(ctx->d_query + where_at);
+  const void *total_dev = launch_paths_rooted_count(tape, sbuf, table, docs, root_value, static_cast<const uint8_t *>(root_tag_dev), rows, where, ctx->d_query + 256, prog.levels_at,
+                                                    prog.tokens_at, prog.keys_at, K, offsets, static_cast<uint8_t *>(status_dev), ctx->d_tmp, s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
+  SJ_TRY(ctx, hipMemcpyAsync(total, total_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  const uint64_t matches = *total;
+  *matches_out = matches;
+  if (matches > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
+  if (matches > match_cap) { return SJGPU_E_OVERFLOW; }
+  if (matches) {
+    launch_paths_rooted_fill(tape, sbuf, table, root_value, rows, where, ctx->d_query + 256, prog.levels_at, prog.tokens_at, prog.keys_at, K, offsets,
+                             static_cast<uint64_t *>(value_dev), static_cast<uint8_t *>(tag_dev), s);
+    SJ_TRY(ctx, hipGetLastError());
+    SJ_TRY(ctx, hipStreamSynchronize(s)); // (the program block, the verdicts and the workspace are free again when the call returns)
+  }
   return 0;
 }
 

@@ -309,6 +309,15 @@ const void *launch_paths_count(const uint64_t *tape, const uint8_t *string_buf, 
 // behind it, when the total fits: match j of cell c to value / tag[offsets[c] + j], never at or beyond offsets[c + 1]
 void launch_paths_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program, uint32_t levels_at, uint32_t tokens_at,
                        uint32_t keys_at, uint32_t K, const uint32_t *offsets, uint64_t *value, uint8_t *tag, hipStream_t s);
+// ---- the paths rooted at the cells of one row (sjgpu_query.hip: sjgpu_at_paths_from_cells_device, include/sjgpu_lists.h) ------------------------------------------
+// launch_paths_count / launch_paths_fill with `rows` root cells in the place of the documents: K >= 1, rows >= 1, docs >= 0, K * rows + 1 entries the scan takes,
+// workspace paths_workspace_bytes(K, rows); where[0 .. rows) (device memory): the roots' verdicts, which k_rows_locate leaves in front of the count and the fill reads again
+const void *launch_paths_rooted_count(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value,
+                                      const uint8_t *root_tag, uint32_t rows, uint32_t *where, const uint8_t *program, uint32_t levels_at, uint32_t tokens_at, uint32_t keys_at,
+                                      uint32_t K, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s);
+void launch_paths_rooted_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, const uint64_t *root_value, uint32_t rows, const uint32_t *where,
+                              const uint8_t *program, uint32_t levels_at, uint32_t tokens_at, uint32_t keys_at, uint32_t K, const uint32_t *offsets, uint64_t *value, uint8_t *tag,
+                              hipStream_t s);
 // ---- the same cells, breadth first (sjgpu_query.hip: sjgpu_at_paths_wide_device) ------------------------------------------------------------------------
 // The whole call behind the table check, K >= 1 and docs >= 1: the annotation of the tape (a head bit and a nesting depth per word), the starting frontier, the
 // levels of every path with their 4-byte read-backs of frontier sizes (into *readback: host memory, pinned where the copy is a real one), statuses, offsets and

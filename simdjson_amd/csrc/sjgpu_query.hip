@@ -1,6 +1,7 @@
 // simdjson_amd/csrc/sjgpu_query.hip -- queries over device tapes: a batched dom::element::at_pointer (sjgpu_at_pointers_device) and the
 // string column as offsets + characters (sjgpu_gather_strings_device).  Contract: include/sjgpu_query.h.  The same walk rooted at the cells of a
-// column (sjgpu_at_pointers_from_cells_device, include/sjgpu_rows.h) is at the end of the kernels.
+// column (sjgpu_at_pointers_from_cells_device, include/sjgpu_rows.h) is at the end of the kernels, and behind it the paths rooted the same way
+// (sjgpu_at_paths_from_cells_device, include/sjgpu_lists.h).
 //
 // The walk.  K pointers x docs documents = K * docs CELLS; one lane walks one cell, the lanes of a workgroup take consecutive documents of ONE
 // pointer: the column stores are coalesced, the workgroup's pointer -- its tokens as sj_query_program.h compiled them and its
@@ -289,6 +290,128 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_gather_copy(const u8 *__restr
 // indexed by the stack pointer would live in scratch memory.  The frames' levels and kinds (object: a key word lies in front of every value) are eight
 // bytes of one register.  A container's end is cut to the end of the frame it was reached from, so the children of two siblings never overlap and a
 // cell's work stays linear in the words of its document whatever the tape says.
+// path ph of the program into the workgroup's LDS, by all of its lanes: its levels, its tokens and its key area.  Ends behind the barrier.  The prologue of
+// k_at_paths and of k_at_paths_rooted.
+__device__ __forceinline__ void stage_path(const u8 *__restrict__ prog, u32 levels_at, u32 tokens_at, u32 keys_at, const path_header &ph, path_level *s_lev /* LDS */,
+                                           query_token *s_tok /* LDS */, u64 *s_key /* LDS */) {
+  const u32 tid = threadIdx.x;
+  const u32 n_lev = ph.levels < PATH_MAX_LEVELS ? ph.levels : PATH_MAX_LEVELS, n_tok = ph.tokens < PATH_MAX_TOKENS ? ph.tokens : PATH_MAX_TOKENS;
+  const u64 *lsrc = reinterpret_cast<const u64 *>(prog + levels_at) + u64(ph.first_level) * (sizeof(path_level) / 8);
+  u64 *ldst = reinterpret_cast<u64 *>(s_lev);
+  for (u32 j = tid; j < n_lev * u32(sizeof(path_level) / 8); j += QUERY_THREADS) { ldst[j] = lsrc[j]; }
+  const u64 *src = reinterpret_cast<const u64 *>(prog + tokens_at) + u64(ph.first_token) * (sizeof(query_token) / 8);
+  u64 *dst = reinterpret_cast<u64 *>(s_tok);
+  for (u32 j = tid; j < n_tok * u32(sizeof(query_token) / 8); j += QUERY_THREADS) { dst[j] = src[j]; }
+  u32 key_words = 0;
+  if (n_tok) {
+    const query_token last = reinterpret_cast<const query_token *>(prog + tokens_at)[ph.first_token + n_tok - 1u];
+    key_words = (last.key_off + last.key_len + 7u) / 8u;
+  }
+  key_words = key_words < QUERY_KEY_AREA / 8 ? key_words : QUERY_KEY_AREA / 8;
+  const u64 *ksrc = reinterpret_cast<const u64 *>(prog + keys_at + ph.keys_at);
+  for (u32 j = tid; j < key_words; j += QUERY_THREADS) { s_key[j] = ksrc[j]; }
+  lds_writes_done();
+  __syncthreads();
+}
+
+// One at_path_with_wildcard: the levels s_lev[0 .. levels) asked of the element that begins at word `cur` (its word: w).  outer: the end of what surrounds the
+// element (the document, or the root cell's own end); no level is followed beyond it.  base / doc_end / str_base / str_end: the four bounds of the element's
+// document.  FILL: the matches go to value / tag[out .. out_end); else they are counted.  code: the status, set at level 0 only.  The walk of k_at_paths and of
+// k_at_paths_rooted.
+template <bool FILL>
+__device__ __forceinline__ void walk_levels(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const path_level *s_lev /* LDS */, u32 levels, const query_token *s_tok /* LDS */,
+                                            const u8 *keys /* LDS, 8-byte aligned */, u32 (*s_cur)[QUERY_THREADS] /* LDS */, u32 (*s_end)[QUERY_THREADS] /* LDS */, u64 cur, u64 w,
+                                            u64 outer, u64 base, u64 doc_end, u64 str_base, u64 str_end, u32 &count, u32 &code, u64 out, u64 out_end, u64 *__restrict__ value,
+                                            u8 *__restrict__ tag) {
+  const u32 tid = threadIdx.x;
+  auto emit = [&](u64 at, u64 ew) {
+    if (FILL) {
+      if (out < out_end) { // never at or beyond the next cell's first match, whatever the tape says
+        tag[out] = u8(ew >> 56);
+        value[out] = cell_value(tape, sbuf, at, ew, base, doc_end, str_base, str_end);
+        out++;
+      }
+    } else {
+      count++;
+    }
+  };
+  u32 L = 0, sp = 0;
+  u64 frames = 0; // byte s: the level of frame s, bit 7: the frame walks an object
+  bool have = true;
+  for (;;) {
+    if (have) {
+      have = false;
+      const u32 kind = u32(w >> 56);
+      if (!is_container_tag(kind)) { continue; } // a scalar contributes nothing at any level, and is no error
+      const u64 limit = sp ? base + s_end[sp - 1u][tid] : outer;
+      const path_level lv = s_lev[L];
+      if (lv.kind == PATH_PTR || lv.kind == PATH_TAIL) {
+        const u32 c = walk_tokens(tape, sbuf, s_tok + lv.first_token, lv.tokens, keys, base, limit, str_base, str_end, cur, w);
+        if (lv.kind == PATH_PTR) {
+          if (!c && L + 1u < levels) { L++; have = true; }
+        } else if (c) {
+          if (L == 0) { code = c; }
+        } else {
+          emit(cur, w);
+        }
+      } else if (lv.kind == PATH_WILD || lv.kind == PATH_WILD_LAST) {
+        const u32 obj = kind == '{' ? 1u : 0u;
+        u64 end = base + (w & LOW32);
+        end = end > cur ? end - 1u : cur; // the closing word
+        end = end < limit ? end : limit;
+        u64 i = cur + 1u + obj; // the first child's value
+        if (lv.kind == PATH_WILD_LAST) {
+          while (i < end) {
+            const u64 ew = tape[i];
+            emit(i, ew);
+            i = behind(i, ew, base, end) + obj;
+          }
+        } else if (i < end && sp < PATH_MAX_WILDS && L + 1u < levels) {
+          s_cur[sp][tid] = u32(i - base);
+          s_end[sp][tid] = u32(end - base);
+          frames = (frames & ~(0xFFull << (8u * sp))) | (u64(L | (obj << 7)) << (8u * sp));
+          sp++;
+        }
+      } else if (L == 0) {
+        code = QUERY_INVALID_JSON_POINTER; // ERR22
+      }
+    } else {
+      if (sp == 0) { break; }
+      const u32 f = u32(frames >> (8u * (sp - 1u))) & 0xFFu;
+      const u64 end = base + s_end[sp - 1u][tid], i = base + s_cur[sp - 1u][tid];
+      if (i < end) {
+        cur = i;
+        w = tape[i];
+        const u64 next = behind(i, w, base, end) + (f >> 7);
+        s_cur[sp - 1u][tid] = u32((next < end ? next : end) - base);
+        L = (f & 31u) + 1u;
+        have = true;
+      } else {
+        sp--;
+      }
+    }
+  }
+}
+
+// what the count leaves: the cell's count and status, the scan's last entry, the workgroup's sum in 64 bits.  The epilogue of k_at_paths<false> and of
+// k_at_paths_rooted<false>; lanes: the cells of one path (documents, or roots)
+__device__ __forceinline__ void paths_count_done(bool active, u64 cell, u32 count, u32 code, u32 lanes, u32 row_blocks, u32 *__restrict__ offsets, u8 *__restrict__ status,
+                                                 u64 *__restrict__ block_sums, u64 *s_sum /* LDS */) {
+  const u32 tid = threadIdx.x;
+  if (active) {
+    offsets[cell] = code ? 0u : count;
+    status[cell] = u8(code);
+    if (cell == 0) { offsets[u64(gridDim.x / row_blocks) * lanes] = 0; } // the scan's last entry: the total lands there
+  }
+  u64 sum = code ? 0u : count;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); }
+  if (lane_id() == 0) { s_sum[tid >> 6] = sum; }
+  lds_writes_done();
+  __syncthreads();
+  if (tid == 0) { block_sums[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]; }
+}
+
 // grid: K rows of row_blocks workgroups, row k = path k
 template <bool FILL>
 __global__ __launch_bounds__(QUERY_THREADS) void k_at_paths(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table, u32 docs,
@@ -301,25 +424,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_paths(const u64 *__restric
   __shared__ u64 s_sum[QUERY_THREADS / 64];
   const u32 k = blockIdx.x / row_blocks, row_block = blockIdx.x - k * row_blocks, tid = threadIdx.x;
   const path_header ph = reinterpret_cast<const path_header *>(prog)[k];
-  {
-    const u32 n_lev = ph.levels < PATH_MAX_LEVELS ? ph.levels : PATH_MAX_LEVELS, n_tok = ph.tokens < PATH_MAX_TOKENS ? ph.tokens : PATH_MAX_TOKENS;
-    const u64 *lsrc = reinterpret_cast<const u64 *>(prog + levels_at) + u64(ph.first_level) * (sizeof(path_level) / 8);
-    u64 *ldst = reinterpret_cast<u64 *>(s_lev);
-    for (u32 j = tid; j < n_lev * u32(sizeof(path_level) / 8); j += QUERY_THREADS) { ldst[j] = lsrc[j]; }
-    const u64 *src = reinterpret_cast<const u64 *>(prog + tokens_at) + u64(ph.first_token) * (sizeof(query_token) / 8);
-    u64 *dst = reinterpret_cast<u64 *>(s_tok);
-    for (u32 j = tid; j < n_tok * u32(sizeof(query_token) / 8); j += QUERY_THREADS) { dst[j] = src[j]; }
-    u32 key_words = 0;
-    if (n_tok) {
-      const query_token last = reinterpret_cast<const query_token *>(prog + tokens_at)[ph.first_token + n_tok - 1u];
-      key_words = (last.key_off + last.key_len + 7u) / 8u;
-    }
-    key_words = key_words < QUERY_KEY_AREA / 8 ? key_words : QUERY_KEY_AREA / 8;
-    const u64 *ksrc = reinterpret_cast<const u64 *>(prog + keys_at + ph.keys_at);
-    for (u32 j = tid; j < key_words; j += QUERY_THREADS) { s_key[j] = ksrc[j]; }
-  }
-  lds_writes_done();
-  __syncthreads();
+  stage_path(prog, levels_at, tokens_at, keys_at, ph, s_lev, s_tok, s_key);
   const u64 d64 = u64(row_block) * QUERY_THREADS + tid;
   const bool active = d64 < docs;
   const u64 cell = u64(k) * docs + d64;
@@ -336,90 +441,13 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_paths(const u64 *__restric
     const uint4 a = *reinterpret_cast<const uint4 *>(table + d), b = *reinterpret_cast<const uint4 *>(table + d + 1u);
     const u64 base = a.z, doc_end = b.z; // the document's words: [base, doc_end)
     const u64 str_base = a.w, str_end = b.w;
-    const u8 *keys = reinterpret_cast<const u8 *>(s_key);
-    auto emit = [&](u64 at, u64 ew) {
-      if (FILL) {
-        if (out < out_end) { // never at or beyond the next cell's first match, whatever the tape says
-          tag[out] = u8(ew >> 56);
-          value[out] = cell_value(tape, sbuf, at, ew, base, doc_end, str_base, str_end);
-          out++;
-        }
-      } else {
-        count++;
-      }
-    };
-    u64 cur = base + 1u; // the root: behind the root word
-    u64 w = cur < doc_end ? tape[cur] : 0; // (no root: a tag that is no container's)
-    u32 L = 0, sp = 0;
-    u64 frames = 0; // byte s: the level of frame s, bit 7: the frame walks an object
-    bool have = true;
-    for (;;) {
-      if (have) {
-        have = false;
-        const u32 kind = u32(w >> 56);
-        if (!is_container_tag(kind)) { continue; } // a scalar contributes nothing at any level, and is no error
-        const u64 limit = sp ? base + s_end[sp - 1u][tid] : doc_end;
-        const path_level lv = s_lev[L];
-        if (lv.kind == PATH_PTR || lv.kind == PATH_TAIL) {
-          const u32 c = walk_tokens(tape, sbuf, s_tok + lv.first_token, lv.tokens, keys, base, limit, str_base, str_end, cur, w);
-          if (lv.kind == PATH_PTR) {
-            if (!c && L + 1u < ph.levels) { L++; have = true; }
-          } else if (c) {
-            if (L == 0) { code = c; }
-          } else {
-            emit(cur, w);
-          }
-        } else if (lv.kind == PATH_WILD || lv.kind == PATH_WILD_LAST) {
-          const u32 obj = kind == '{' ? 1u : 0u;
-          u64 end = base + (w & LOW32);
-          end = end > cur ? end - 1u : cur; // the closing word
-          end = end < limit ? end : limit;
-          u64 i = cur + 1u + obj; // the first child's value
-          if (lv.kind == PATH_WILD_LAST) {
-            while (i < end) {
-              const u64 ew = tape[i];
-              emit(i, ew);
-              i = behind(i, ew, base, end) + obj;
-            }
-          } else if (i < end && sp < PATH_MAX_WILDS && L + 1u < ph.levels) {
-            s_cur[sp][tid] = u32(i - base);
-            s_end[sp][tid] = u32(end - base);
-            frames = (frames & ~(0xFFull << (8u * sp))) | (u64(L | (obj << 7)) << (8u * sp));
-            sp++;
-          }
-        } else if (L == 0) {
-          code = QUERY_INVALID_JSON_POINTER; // ERR22
-        }
-      } else {
-        if (sp == 0) { break; }
-        const u32 f = u32(frames >> (8u * (sp - 1u))) & 0xFFu;
-        const u64 end = base + s_end[sp - 1u][tid], i = base + s_cur[sp - 1u][tid];
-        if (i < end) {
-          cur = i;
-          w = tape[i];
-          const u64 next = behind(i, w, base, end) + (f >> 7);
-          s_cur[sp - 1u][tid] = u32((next < end ? next : end) - base);
-          L = (f & 31u) + 1u;
-          have = true;
-        } else {
-          sp--;
-        }
-      }
-    }
+    const u64 cur = base + 1u; // the root: behind the root word
+    const u64 w = cur < doc_end ? tape[cur] : 0; // (no root: a tag that is no container's)
+    walk_levels<FILL>(tape, sbuf, s_lev, ph.levels, s_tok, reinterpret_cast<const u8 *>(s_key), s_cur, s_end, cur, w, doc_end, base, doc_end, str_base, str_end, count, code, out,
+                      out_end, value, tag);
   }
   if (FILL) { return; }
-  if (active) {
-    offsets[cell] = code ? 0u : count;
-    status[cell] = u8(code);
-    if (cell == 0) { offsets[u64(gridDim.x / row_blocks) * docs] = 0; } // the scan's last entry: the total lands there
-  }
-  u64 sum = code ? 0u : count;
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); }
-  if (lane_id() == 0) { s_sum[tid >> 6] = sum; }
-  lds_writes_done();
-  __syncthreads();
-  if (tid == 0) { block_sums[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]; }
+  paths_count_done(active, cell, count, code, docs, row_blocks, offsets, status, block_sums, s_sum);
 }
 
 // ---- the paths, wide (include/sjgpu_paths.h: sjgpu_at_paths_wide_device) --------------------------------------------------------------------------
@@ -809,6 +837,54 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_pointers_rooted(const u64 
   value[cell] = out_value;
 }
 
+// ---- the lists (include/sjgpu_lists.h: sjgpu_at_paths_from_cells_device) ----------------------------------------------------------------------------
+// at_path_with_wildcard of K paths rooted at the CELLS of one row: K x rows cells, one lane each, mapped and counted / scanned / filled like k_at_paths.  What a
+// root is comes from k_rows_locate, once per call for all K paths and both passes: a located container walks from its opening word, bounded by the cell's high
+// half cut to its document's end; a scalar root is status 0 without a match; everything else its code (a disagreeing cell: 20) without a match -- whatever the path.
+// grid: K rows of row_blocks workgroups, row k = path k; lane = root
+template <bool FILL>
+__global__ __launch_bounds__(QUERY_THREADS) void k_at_paths_rooted(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table,
+                                                                 const u64 *__restrict__ root_value, const u32 *__restrict__ where, u32 rows, const u8 *__restrict__ prog,
+                                                                 u32 levels_at, u32 tokens_at, u32 keys_at, u32 row_blocks, u32 *__restrict__ offsets, u8 *__restrict__ status,
+                                                                 u64 *__restrict__ block_sums, u64 *__restrict__ value, u8 *__restrict__ tag) {
+  __shared__ query_token s_tok[PATH_MAX_TOKENS];
+  __shared__ u64 s_key[QUERY_KEY_AREA / 8];
+  __shared__ path_level s_lev[PATH_MAX_LEVELS];
+  __shared__ u32 s_cur[PATH_MAX_WILDS][QUERY_THREADS], s_end[PATH_MAX_WILDS][QUERY_THREADS];
+  __shared__ u64 s_sum[QUERY_THREADS / 64];
+  const u32 k = blockIdx.x / row_blocks, row_block = blockIdx.x - k * row_blocks, tid = threadIdx.x;
+  const path_header ph = reinterpret_cast<const path_header *>(prog)[k];
+  stage_path(prog, levels_at, tokens_at, keys_at, ph, s_lev, s_tok, s_key);
+  const u64 r64 = u64(row_block) * QUERY_THREADS + tid;
+  const bool active = r64 < rows;
+  const u64 cell = u64(k) * rows + r64;
+  u32 count = 0, code = 0;
+  u64 out = 0, out_end = 0; // FILL: the cell's matches are value / tag[out .. out_end)
+  bool go = active;
+  if (FILL && active) {
+    out = offsets[cell];
+    out_end = offsets[cell + 1u];
+    go = out < out_end; // (a cell without matches, or with a status, has nothing to write)
+  }
+  if (go) {
+    const u32 m = where[r64];
+    if (m > ROWS_SPECIAL) {
+      code = (m & 15u) + 16u;
+    } else if (m < ROWS_SPECIAL) { // (ROWS_SPECIAL itself: a scalar, status 0 and nothing)
+      const uint4 a = *reinterpret_cast<const uint4 *>(table + m), b = *reinterpret_cast<const uint4 *>(table + m + 1u);
+      const u64 base = a.z, doc_end = b.z;
+      const u64 str_base = a.w, str_end = b.w;
+      const u64 v = root_value[r64];
+      const u64 cur = v & LOW32, w = tape[cur]; // (k_rows_locate found cur inside the document, and w to agree with the cell)
+      const u64 outer = (v >> 32) < doc_end ? (v >> 32) : doc_end;
+      walk_levels<FILL>(tape, sbuf, s_lev, ph.levels, s_tok, reinterpret_cast<const u8 *>(s_key), s_cur, s_end, cur, w, outer, base, doc_end, str_base, str_end, count, code, out,
+                        out_end, value, tag);
+    }
+  }
+  if (FILL) { return; }
+  paths_count_done(active, cell, count, code, rows, row_blocks, offsets, status, block_sums, s_sum);
+}
+
 static inline u32 blocks_of(u64 n, u32 per) { return u32((n + per - 1) / per); }
 
 } // namespace
@@ -876,6 +952,31 @@ void launch_paths_fill(const uint64_t *tape, const uint8_t *string_buf, const do
   const u32 row_blocks = blocks_of(docs, QUERY_THREADS);
   hipLaunchKernelGGL(k_at_paths<true>, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, docs, program, levels_at, tokens_at, keys_at, row_blocks,
                      const_cast<u32 *>(offsets), static_cast<u8 *>(nullptr), static_cast<u64 *>(nullptr), value, tag);
+}
+
+// the same count and fill rooted at the cells of one row (include/sjgpu_lists.h); where[0 .. rows): k_rows_locate's verdicts, made here in front of the count
+const void *launch_paths_rooted_count(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value,
+                                      const uint8_t *root_tag, uint32_t rows, uint32_t *where, const uint8_t *program, uint32_t levels_at, uint32_t tokens_at, uint32_t keys_at,
+                                      uint32_t K, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s) {
+  uint8_t *ws = static_cast<uint8_t *>(workspace);
+  gather_ctrl *ctrl = reinterpret_cast<gather_ctrl *>(ws);
+  u64 *block_sums = reinterpret_cast<u64 *>(ws + 256);
+  int *partial = reinterpret_cast<int *>(ws + 256 + paths_sums_bytes(K, rows));
+  const u32 row_blocks = blocks_of(rows, QUERY_THREADS), cells = K * rows;
+  hipLaunchKernelGGL(k_rows_locate, dim3(row_blocks), dim3(QUERY_THREADS), 0, s, tape, table, docs, root_value, root_tag, rows, where);
+  hipLaunchKernelGGL(k_at_paths_rooted<false>, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, root_value, static_cast<const u32 *>(where), rows, program,
+                     levels_at, tokens_at, keys_at, row_blocks, offsets, status, block_sums, static_cast<u64 *>(nullptr), static_cast<u8 *>(nullptr));
+  hipLaunchKernelGGL(k_gather_total, dim3(1), dim3(QUERY_THREADS), 0, s, block_sums, row_blocks * K, cells, ctrl);
+  enqueue_scan(reinterpret_cast<int *>(offsets), cells + 1u, &ctrl->n_plus_1, partial, s);
+  return ctrl;
+}
+
+void launch_paths_rooted_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, const uint64_t *root_value, uint32_t rows, const uint32_t *where,
+                              const uint8_t *program, uint32_t levels_at, uint32_t tokens_at, uint32_t keys_at, uint32_t K, const uint32_t *offsets, uint64_t *value, uint8_t *tag,
+                              hipStream_t s) {
+  const u32 row_blocks = blocks_of(rows, QUERY_THREADS);
+  hipLaunchKernelGGL(k_at_paths_rooted<true>, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, root_value, where, rows, program, levels_at, tokens_at,
+                     keys_at, row_blocks, const_cast<u32 *>(offsets), static_cast<u8 *>(nullptr), static_cast<u64 *>(nullptr), value, tag);
 }
 
 // ---- the wide call's level loop ---------------------------------------------------------------------------------------------------------------------
