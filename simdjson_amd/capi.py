@@ -68,6 +68,40 @@ ROWS_EXPORTS = ["sjgpu_at_pointers_from_cells_device"]
 LISTS_EXPORTS = ["sjgpu_at_paths_from_cells_device"]
 
 
+# what include/sjgpu_cast.h declares (typed getters over a column: get<T> per cell with validity bits, and the census of a column's tags)
+CAST_EXPORTS = ["sjgpu_cell_kinds_device", "sjgpu_cast_cells_device"]
+# SJGPU_GET_*: the getter a row of sjgpu_cast_cells_device asks of its cells
+GET_INT64, GET_UINT64, GET_DOUBLE, GET_BOOL, GET_STRING, GET_ARRAY, GET_OBJECT = 1, 2, 3, 4, 5, 6, 7
+NUMBER_OUT_OF_RANGE = 18  # what get_int64 answers a u cell, get_uint64 a negative l
+
+
+def infer_getters(kinds):
+    """The getter a loader would ask of each row, from its census (kinds: K x 16 counts as sjgpu_cell_kinds_device leaves them) -> list of K SJGPU_GET_* or 0.
+    The ELEMENTS of a row are its cells except the nulls and the codes 17 / 19 / 20 / 22 (they become invalid bits under any getter):
+    all t / f: BOOL; all strings: STRING; all arrays: ARRAY; all objects: OBJECT; numbers only: DOUBLE when there is a d, else INT64 without a u, else UINT64
+    without a negative l, else -- a u beside a negative l, no 64-bit integer holds both -- DOUBLE, which is LOSSY above 2^53 as get_double is.
+    No elements, a mix of kinds or a byte that is no tag: 0, "leave the row as cells"."""
+    picked = []
+    for row in np.asarray(kinds).reshape(-1, 16).tolist():
+        n_obj, n_arr, n_str, n_l, n_u, n_d, n_t, n_f, _, n_neg = row[:10]
+        elements = n_obj + n_arr + n_str + n_l + n_u + n_d + n_t + n_f + row[14]
+        if elements == 0:
+            picked.append(0)
+        elif n_t + n_f == elements:
+            picked.append(GET_BOOL)
+        elif n_str == elements:
+            picked.append(GET_STRING)
+        elif n_arr == elements:
+            picked.append(GET_ARRAY)
+        elif n_obj == elements:
+            picked.append(GET_OBJECT)
+        elif n_l + n_u + n_d == elements:
+            picked.append(GET_DOUBLE if n_d or (n_u and n_neg) else GET_UINT64 if n_u else GET_INT64)
+        else:
+            picked.append(0)
+    return picked
+
+
 class ScanResult(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("out_len", ctypes.c_uint64)]
 
@@ -170,6 +204,10 @@ def load_library():
     L.sjgpu_at_paths_from_cells_device.restype = ctypes.c_int
     L.sjgpu_at_paths_from_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp,
                                                    ctypes.c_uint64, vp, u64p]
+    L.sjgpu_cell_kinds_device.restype = ctypes.c_int
+    L.sjgpu_cell_kinds_device.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    L.sjgpu_cast_cells_device.restype = ctypes.c_int
+    L.sjgpu_cast_cells_device.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int
@@ -644,12 +682,20 @@ class DomParserImplementation:
         sjgpu_at_paths_wide_device) and sjgpu_at_pointers_from_cells_device over its matches, with everything resident (the twin of extract_many and explode_many).
         Row r of the table is match r of the path; the rows of document d are row_offsets[d] .. row_offsets[d + 1] (a document whose status is not 0 has none).
         -> (error_code of the first broken document or 0, documents delivered, row_offsets uint32[docs + 1], tags uint8[K, rows], values uint64[K, rows])"""
+        code, docs, offsets, tags, values, _ = self._table_cells(data, row_path, pointers, max_depth, wide)
+        if offsets is None:
+            return code, docs, np.zeros(docs + 1, np.uint32), np.zeros((len(pointers), 0), np.uint8), np.zeros((len(pointers), 0), np.uint64)
+        return code, docs, offsets.cpu().numpy().view(np.uint32), tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
+
+    def _table_cells(self, data, row_path, pointers, max_depth=1024, wide=False):
+        """table_many's work with the table left on the device -> (code, docs, row_offsets int32[docs + 1], tags uint8[K, rows], values int64[K, rows], (string buffer,
+        its bytes)), all torch tensors of the device, complete (the stream has been waited for); (code, 0, None, None, None, None) when no document was delivered"""
         import torch
         a = _as_u8(data)
         K = len(pointers)
 
         def nothing(code, docs):
-            return code, docs, np.zeros(docs + 1, np.uint32), np.zeros((K, 0), np.uint8), np.zeros((K, 0), np.uint64)
+            return code, docs, None, None, None, None
         if len(a) == 0:
             return nothing(EMPTY, 0)
         dev = torch.device("cuda", self.device)
@@ -691,7 +737,7 @@ class DomParserImplementation:
             if rc:
                 raise SjgpuError(f"sjgpu_at_pointers_from_cells_device refused its arguments ({rc})")
         torch.cuda.current_stream(dev).synchronize()
-        return code, docs, offsets.cpu().numpy().view(np.uint32), tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
+        return code, docs, offsets, tags, values, (sbuf, sb)
 
     def at_paths_from_cells_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, root_value_ptr, root_tag_ptr, rows, paths, offsets_ptr, status_ptr,
                                    value_ptr, tag_ptr, match_cap, stream=0):
@@ -763,6 +809,101 @@ class DomParserImplementation:
         torch.cuda.current_stream(dev).synchronize()
         return (code, docs, row_offsets.cpu().numpy().view(np.uint32), status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(),
                 values[:matches].cpu().numpy().view(np.uint64))
+
+    def cell_kinds_device(self, value_ptr, tag_ptr, n, K, kinds_ptr, stream=0):
+        """sjgpu_cell_kinds_device: the census of K rows of n cells; kinds_ptr -> K * 16 uint32.  Only enqueues.  -> 0 or a negative SJGPU_E_* for arguments the call
+        refuses (raises on HIP errors)"""
+        rc = self.L.sjgpu_cell_kinds_device(self.h, value_ptr or None, tag_ptr or None, int(n), int(K), kinds_ptr or None, stream or None)
+        if rc in (-2, -3):
+            raise SjgpuError(f"sjgpu_cell_kinds_device error {rc}: {self.last_error()}")
+        return rc
+
+    def cast_cells_device(self, value_ptr, tag_ptr, n, getters, value_out_ptr, code_out_ptr, valid_out_ptr, counts_out_ptr, stream=0):
+        """sjgpu_cast_cells_device: row k of the K = len(getters) rows of n cells asks getters[k] (SJGPU_GET_*) of each of its cells; value_out_ptr -> K * n uint64,
+        code_out_ptr -> K * n bytes, valid_out_ptr -> K * ceil(n / 64) uint64, counts_out_ptr -> K * 4 uint32; value_out_ptr / code_out_ptr may be value_ptr / tag_ptr.
+        Only enqueues.  -> 0 or a negative SJGPU_E_* for arguments the call refuses (raises on HIP errors)"""
+        g = np.array(list(getters), dtype=np.uint8)
+        rc = self.L.sjgpu_cast_cells_device(self.h, value_ptr or None, tag_ptr or None, int(n), len(g), g.ctypes.data if len(g) else None, value_out_ptr or None,
+                                            code_out_ptr or None, valid_out_ptr or None, counts_out_ptr or None, stream or None)
+        if rc in (-2, -3):
+            raise SjgpuError(f"sjgpu_cast_cells_device error {rc}: {self.last_error()}")
+        return rc
+
+    def typed_table_many(self, data, row_path, pointers, getters=None, wide=False, max_depth=1024):
+        """table_many with typed columns: its cells stay on the device, sjgpu_cell_kinds_device takes their census, infer_getters picks a getter per column where
+        `getters` (a list of SJGPU_GET_* or 0 per pointer) gives none, ONE sjgpu_cast_cells_device call casts the columns that have a getter, and
+        sjgpu_gather_strings_device turns every STRING column into offsets + characters (its invalid cells have length 0).
+        -> (error_code of the first broken document or 0, documents delivered, row_offsets uint32[docs + 1], columns), columns: one dict per pointer with
+            "getter"  SJGPU_GET_* or 0 (left as cells)         "kinds"   the column's census, uint32[16]
+            "tags", "cells"   the column as table_many returns it, uint8[rows] / uint64[rows]
+          and, with a getter,
+            "values"  int64 / uint64 / float64 / bool [rows]; the cells' words (uint64) for ARRAY and OBJECT; for STRING "offsets" uint32[rows + 1] and "chars" uint8
+            "valid"   the Arrow validity buffer, uint8[ceil(rows / 64) * 8], least significant bit first      "codes"  uint8[rows], 0 = valid
+            "counts"  uint32[4]: valid cells, nulls, NUMBER_OUT_OF_RANGE cells, cells that held a code before the cast"""
+        import torch
+        K = len(pointers)
+        code, docs, offsets, tags, values, strings = self._table_cells(data, row_path, pointers, max_depth, wide)
+        if offsets is None:
+            return code, docs, np.zeros(docs + 1, np.uint32), [{"getter": 0, "kinds": np.zeros(16, np.uint32), "tags": np.zeros(0, np.uint8), "cells": np.zeros(0, np.uint64)}
+                                                                for _ in range(K)]
+        dev = tags.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rows = tags.shape[1]
+        kinds = torch.empty((K, 16), dtype=torch.int32, device=dev)
+        if K:
+            rc = self.cell_kinds_device(values.data_ptr(), tags.data_ptr(), rows, K, kinds.data_ptr(), stream)
+            if rc:
+                raise SjgpuError(f"sjgpu_cell_kinds_device refused its arguments ({rc})")
+        kinds_h = kinds.cpu().numpy().view(np.uint32)
+        inferred = infer_getters(kinds_h)
+        picked = [inferred[k] if getters is None or not getters[k] else int(getters[k]) for k in range(K)]
+        cast = [k for k in range(K) if picked[k]]
+        tags_h, cells_h = tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
+        columns = [{"getter": picked[k], "kinds": kinds_h[k], "tags": tags_h[k], "cells": cells_h[k]} for k in range(K)]
+        if not cast:
+            return code, docs, offsets.cpu().numpy().view(np.uint32), columns
+        C, W = len(cast), (rows + 63) // 64
+        index = torch.tensor(cast, dtype=torch.int64, device=dev)
+        in_values, in_tags = values.index_select(0, index).contiguous(), tags.index_select(0, index).contiguous()  # the rows with a getter, back to back
+        out_values = torch.empty((C, rows), dtype=torch.int64, device=dev)
+        out_codes = torch.empty((C, rows), dtype=torch.uint8, device=dev)
+        valid = torch.empty((C, W), dtype=torch.int64, device=dev)
+        counts = torch.empty((C, 4), dtype=torch.int32, device=dev)
+        rc = self.cast_cells_device(in_values.data_ptr(), in_tags.data_ptr(), rows, [picked[k] for k in cast], out_values.data_ptr(), out_codes.data_ptr(), valid.data_ptr(),
+                                    counts.data_ptr(), stream)
+        if rc:
+            raise SjgpuError(f"sjgpu_cast_cells_device refused its arguments ({rc})")
+        sbuf, sb = strings
+        gathered = {}
+        for j, k in enumerate(cast):
+            if picked[k] != GET_STRING:
+                continue
+            # a cell that is no string has code != 0 and value 0; the gather wants the tags: the valid cells of a STRING column are exactly its `"` cells
+            soff = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+            rc, total = self.gather_strings_device(sbuf.data_ptr(), sb, in_values[j].data_ptr(), in_tags[j].data_ptr(), rows, soff.data_ptr(), 0, 0, stream)
+            chars = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+            if rc == -5:
+                rc, total = self.gather_strings_device(sbuf.data_ptr(), sb, in_values[j].data_ptr(), in_tags[j].data_ptr(), rows, soff.data_ptr(), chars.data_ptr(), total, stream)
+            if rc:
+                raise SjgpuError(f"sjgpu_gather_strings_device refused its arguments ({rc})")
+            gathered[k] = (soff, chars[:total])
+        torch.cuda.current_stream(dev).synchronize()
+        out_h, codes_h, valid_h, counts_h = out_values.cpu().numpy(), out_codes.cpu().numpy(), valid.cpu().numpy(), counts.cpu().numpy().view(np.uint32)
+        for j, k in enumerate(cast):
+            col = columns[k]
+            col["codes"], col["counts"], col["valid"] = codes_h[j], counts_h[j], valid_h[j].view(np.uint8)
+            g = picked[k]
+            if g == GET_STRING:
+                col["offsets"], col["chars"] = gathered[k][0].cpu().numpy().view(np.uint32), gathered[k][1].cpu().numpy()
+            elif g == GET_INT64:
+                col["values"] = out_h[j]
+            elif g == GET_DOUBLE:
+                col["values"] = out_h[j].view(np.float64)
+            elif g == GET_BOOL:
+                col["values"] = out_h[j] != 0
+            else:
+                col["values"] = out_h[j].view(np.uint64)
+        return code, docs, offsets.cpu().numpy().view(np.uint32), columns
 
     def result(self, stream=0):  # waits for `stream`
         r = ScanResult()

@@ -1,4 +1,4 @@
-// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h, include/sjgpu_query.h, include/sjgpu_paths.h, include/sjgpu_rows.h and include/sjgpu_lists.h, what follows the structural list on the device: the strings of a
+// simdjson_amd/csrc/sjgpu_capi_stage2.hip -- the C-ABI of include/sjgpu.h, include/sjgpu_stream.h, include/sjgpu_query.h, include/sjgpu_paths.h, include/sjgpu_rows.h, include/sjgpu_lists.h and include/sjgpu_cast.h, what follows the structural list on the device: the strings of a
 // document, On-Demand's raw key comparison, stage 2 (the DOM tape of a document, the tapes of a document stream), sjgpu_parse and sjgpu_parse_many, and the queries over the tapes
 // (JSON pointers -> typed columns, a string column -> offsets + characters).  Shared with the other units: sjgpu_ctx.h.
 #include "sjgpu_ctx.h"
@@ -6,6 +6,7 @@
 #include "sjgpu_paths.h"
 #include "sjgpu_rows.h"
 #include "sjgpu_lists.h"
+#include "sjgpu_cast.h"
 #include "sj_path_program.h"
 
 extern "C" {
@@ -621,6 +622,28 @@ int sjgpu_at_paths_from_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint6
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s)); // (the program block, the verdicts and the workspace are free again when the call returns)
   }
+  return 0;
+}
+
+// ---- typed getters over cells (k_cell_kinds, k_cast_cells in sjgpu_cast.hip; include/sjgpu_cast.h) ------------------------------------------------------
+// Elementwise over the cells alone: no block of the context, no upload, no event, no wait -- a memset of the counters and one launch, only enqueued
+int sjgpu_cell_kinds_device(sjgpu_ctx *ctx, const void *value_dev, const void *tag_dev, uint32_t n, uint32_t K, void *kinds_dev, void *stream) {
+  if (!ctx || !cell_kinds_args_ok(value_dev, tag_dev, n, K, kinds_dev)) { return SJGPU_E_BADARG; }
+  if (K == 0) { return 0; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  SJ_TRY(ctx, launch_cell_kinds(static_cast<const uint64_t *>(value_dev), static_cast<const uint8_t *>(tag_dev), n, K, static_cast<uint32_t *>(kinds_dev), pick(ctx, stream)));
+  SJ_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+int sjgpu_cast_cells_device(sjgpu_ctx *ctx, const void *value_dev, const void *tag_dev, uint32_t n, uint32_t K, const uint8_t *getters, void *value_out_dev,
+                            void *code_out_dev, void *valid_out_dev, void *counts_out_dev, void *stream) {
+  if (!ctx || !cast_cells_args_ok(value_dev, tag_dev, n, K, getters, value_out_dev, code_out_dev, valid_out_dev, counts_out_dev)) { return SJGPU_E_BADARG; }
+  if (K == 0) { return 0; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  SJ_TRY(ctx, launch_cast_cells(static_cast<const uint64_t *>(value_dev), static_cast<const uint8_t *>(tag_dev), n, K, getters, static_cast<uint64_t *>(value_out_dev),
+                                static_cast<uint8_t *>(code_out_dev), static_cast<uint64_t *>(valid_out_dev), static_cast<uint32_t *>(counts_out_dev), pick(ctx, stream)));
+  SJ_TRY(ctx, hipGetLastError());
   return 0;
 }
 

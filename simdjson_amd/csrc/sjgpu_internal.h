@@ -329,6 +329,30 @@ size_t paths_wide_workspace_bytes(uint32_t K, uint32_t docs, uint64_t tape_words
 hipError_t launch_paths_wide(const uint64_t *tape, uint64_t tape_words, const uint8_t *string_buf, const doc_span_dev *table, uint32_t docs, const uint8_t *program,
                              const uint8_t *program_host, uint32_t levels_at, uint32_t tokens_at, uint32_t keys_at, uint32_t K, uint32_t *offsets, uint8_t *status,
                              uint64_t *value, uint8_t *tag, uint64_t match_cap, void *workspace, uint32_t *readback, hipStream_t s, uint64_t *matches_out);
+// ---- typed getters over cells (sjgpu_cast.hip: sjgpu_cell_kinds_device, sjgpu_cast_cells_device, include/sjgpu_cast.h) --------------------------------------
+// What the two calls refuse before anything is enqueued (the C-ABI adds the null context): K beyond CAST_MAX_ROWS, the alignments, with K > 0 a null census / counts
+// block / getter list or a getter outside 1 .. 7, with K * n > 0 any other null pointer.  The CPU tier asks the same functions.
+constexpr uint32_t CAST_MAX_ROWS = 64;
+inline bool cast_misaligned(const void *p, uintptr_t align) { return (reinterpret_cast<uintptr_t>(p) & (align - 1)) != 0; }
+inline bool cell_kinds_args_ok(const void *value, const void *tag, uint32_t n, uint32_t K, const void *kinds) {
+  if (K > CAST_MAX_ROWS || cast_misaligned(value, 8) || cast_misaligned(kinds, 4)) { return false; }
+  if (K && !kinds) { return false; }
+  return !(K && n) || (value && tag);
+}
+inline bool cast_cells_args_ok(const void *value, const void *tag, uint32_t n, uint32_t K, const uint8_t *getters, const void *value_out, const void *code_out,
+                               const void *valid_out, const void *counts) {
+  if (K > CAST_MAX_ROWS || cast_misaligned(value, 8) || cast_misaligned(value_out, 8) || cast_misaligned(valid_out, 8) || cast_misaligned(counts, 4)) { return false; }
+  if (K && (!counts || !getters)) { return false; }
+  for (uint32_t k = 0; k < K; k++) {
+    if (getters[k] < 1 || getters[k] > 7) { return false; }
+  }
+  return !(K && n) || (value && tag && value_out && code_out && valid_out);
+}
+// Arguments that passed the check, 1 <= K <= CAST_MAX_ROWS.  A memset of the K * 16 (K * 4) counters and, when n > 0, one launch of K rows of workgroups; the
+// getters ride in the kernel's arguments.  -> what the memset returned (the launch's error is hipGetLastError's)
+hipError_t launch_cell_kinds(const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t K, uint32_t *kinds, hipStream_t s);
+hipError_t launch_cast_cells(const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t K, const uint8_t *getters, uint64_t *value_out, uint8_t *code_out,
+                             uint64_t *valid_out, uint32_t *counts, hipStream_t s);
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);
