@@ -23,7 +23,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from simdjson_amd import build, capi, corpus  # noqa: E402
-from rows_once import POINTERS, Resident  # noqa: E402
+from rows_once import POINTERS  # noqa: E402
 
 
 def host_cast_row(tags, values, getter):
@@ -52,8 +52,9 @@ def main():
     build.build_sjgpu()
     host, statuses = corpus.twitter_like(args.mib << 20, 7)
     p = capi.DomParserImplementation(len(host) + 64)
-    D = Resident(torch, p, host, 1)
-    s = D.s
+    D = capi.ResidentStream(p, host, doc_cap=1)
+    assert (D.code, D.docs) == (0, 1), (D.code, D.docs)
+    s = D.stream
     K = len(POINTERS)
     offsets = torch.empty(2, dtype=torch.int32, device="cuda")
     status = torch.empty(1, dtype=torch.uint8, device="cuda")

@@ -16,50 +16,33 @@ import os
 import statistics
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from simdjson_amd import build, capi, corpus  # noqa: E402
 
 
-class Resident:
-    """a host buffer's stage 1 and its tapes (one per document), everything on the device"""
+def resident(host, doc_cap):
+    """a host buffer's tapes (one per document) on the device, with a parser of its own"""
+    R = capi.ResidentStream(capi.DomParserImplementation(len(host) + 64), host, doc_cap=doc_cap)
+    assert R.code == 0, R.code
+    return R
 
-    def __init__(self, torch, host, doc_cap):
-        self.p = p = capi.DomParserImplementation(len(host) + 64)
-        self.s = s = torch.cuda.current_stream().cuda_stream
-        self.buf = torch.from_numpy(np.concatenate([host, np.zeros(64, np.uint8)])).cuda()
-        self.idx = torch.zeros(len(host) + 16, dtype=torch.int32, device="cuda")
-        assert p.stage1_device(self.buf.data_ptr(), len(host), self.idx.data_ptr(), len(host) + 3, s) == 0
-        n, flags, _ = p.result(s)
-        assert flags == 0, flags
-        sbuf_cap = 5 * (len(host) // 3) + 256
-        self.sbuf = torch.empty(sbuf_cap, dtype=torch.uint8, device="cuda")
-        tape_cap = min(4 * n, len(host) + 3 * doc_cap) + 8
-        self.tape = torch.empty(tape_cap, dtype=torch.int64, device="cuda")
-        self.table = torch.empty((doc_cap + 1) * 4, dtype=torch.int32, device="cuda")
-        code, self.docs, self.tw, self.sb = p.stage2_many_device(self.buf.data_ptr(), len(host), self.idx.data_ptr(), n, self.tape.data_ptr(), tape_cap, self.sbuf.data_ptr(),
-                                                                 sbuf_cap, self.table.data_ptr(), doc_cap + 1, stream=s)
-        assert code == 0, code
-        self.torch = torch
 
-    def paths(self, paths):
-        """-> a function that runs sjgpu_at_paths_device into outputs of the size a first call asked for, and the matches"""
-        torch, p = self.torch, self.p
-        cells = len(paths) * self.docs
-        offsets = torch.empty(cells + 1, dtype=torch.int32, device="cuda")
-        status = torch.empty(cells, dtype=torch.uint8, device="cuda")
-        args = (self.tape.data_ptr(), self.tw, self.sbuf.data_ptr(), self.sb, self.table.data_ptr(), self.docs, paths, offsets.data_ptr(), status.data_ptr())
-        rc, matches = p.at_paths_device(*args, 0, 0, 0, self.s)
-        assert rc in (0, -5), rc
-        values = torch.empty(max(matches, 1), dtype=torch.int64, device="cuda")
-        tags = torch.empty(max(matches, 1), dtype=torch.uint8, device="cuda")
+def paths_run(torch, R, paths):
+    """-> a function that runs sjgpu_at_paths_device into outputs of the size a first call asked for, and the matches"""
+    cells = len(paths) * R.docs
+    offsets = torch.empty(cells + 1, dtype=torch.int32, device="cuda")
+    status = torch.empty(cells, dtype=torch.uint8, device="cuda")
+    args = (*R.args(), paths, offsets.data_ptr(), status.data_ptr())
+    rc, matches = R.p.at_paths_device(*args, 0, 0, 0, R.stream)
+    assert rc in (0, capi.SJGPU_E_OVERFLOW), rc
+    values = torch.empty(max(matches, 1), dtype=torch.int64, device="cuda")
+    tags = torch.empty(max(matches, 1), dtype=torch.uint8, device="cuda")
 
-        def run():
-            rc, m = p.at_paths_device(*args, values.data_ptr(), tags.data_ptr(), matches, self.s)
-            assert (rc, m) == (0, matches), (rc, m)
-        run.keep = (offsets, status, values, tags)
-        return run, matches
+    def run():
+        rc, m = R.p.at_paths_device(*args, values.data_ptr(), tags.data_ptr(), matches, R.stream)
+        assert (rc, m) == (0, matches), (rc, m)
+    run.keep = (offsets, status, values, tags)
+    return run, matches
 
 
 def main():
@@ -74,23 +57,23 @@ def main():
         raise SystemExit("no GPU: this script measures, it does not fall back")
     build.build_sjgpu()
     host, lines = corpus.amazon_ndjson(args.mib << 20, 7)
-    R = Resident(torch, host, lines + 1)
+    R = resident(host, lines + 1)
     assert R.docs == lines, (R.docs, lines)
     top = [b"/%d" % k for k in range(8)]
     values = torch.empty((8, R.docs), dtype=torch.int64, device="cuda")
     tags = torch.empty((8, R.docs), dtype=torch.uint8, device="cuda")
 
     def run_pointers():
-        rc = R.p.at_pointers_device(R.tape.data_ptr(), R.tw, R.sbuf.data_ptr(), R.sb, R.table.data_ptr(), R.docs, top, values.data_ptr(), tags.data_ptr(), R.s)
+        rc = R.p.at_pointers_device(*R.args(), top, values.data_ptr(), tags.data_ptr(), R.stream)
         assert rc == 0, rc
 
-    run_all, all_matches = R.paths([b"$[*]"])
-    run_both, both_matches = R.paths([b"$[*]", b"$[2]"])
+    run_all, all_matches = paths_run(torch, R, [b"$[*]"])
+    run_both, both_matches = paths_run(torch, R, [b"$[*]", b"$[2]"])
     assert all_matches == 9 * R.docs and both_matches == 10 * R.docs, (all_matches, both_matches, R.docs)
     thost, statuses = corpus.twitter_like(args.twitter_mib << 20, 7)
-    W = Resident(torch, thost, 1)
+    W = resident(thost, 1)
     assert W.docs == 1
-    run_ids, id_matches = W.paths([b"$.statuses[*].user.id"])
+    run_ids, id_matches = paths_run(torch, W, [b"$.statuses[*].user.id"])
     assert 0 < id_matches <= statuses, (id_matches, statuses)
 
     def timed(fn):

@@ -21,50 +21,32 @@ import statistics
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-import numpy as np  # noqa: E402
-
 from simdjson_amd import build, capi, corpus  # noqa: E402
 
 TWITTER_PATHS = [b"$.statuses[*].user.id", b"$.statuses[*].entities.hashtags[*].text", b"$.statuses[*].user.entities.hashtags[*].indices[*]"]
 
 
-class Resident:
-    """a host buffer's stage 1 and its tapes (one per document), everything on the device, and what running stage 2 again needs"""
-
-    def __init__(self, torch, host, doc_cap):
-        self.p = p = capi.DomParserImplementation(len(host) + 64)
-        self.s = s = torch.cuda.current_stream().cuda_stream
-        self.length = len(host)
-        self.buf = torch.from_numpy(np.concatenate([host, np.zeros(64, np.uint8)])).cuda()
-        self.idx = torch.zeros(len(host) + 16, dtype=torch.int32, device="cuda")
-        assert p.stage1_device(self.buf.data_ptr(), len(host), self.idx.data_ptr(), len(host) + 3, s) == 0
-        self.n, flags, _ = p.result(s)
-        assert flags == 0, flags
-        self.sbuf = torch.empty(5 * (len(host) // 3) + 256, dtype=torch.uint8, device="cuda")
-        self.tape = torch.empty(min(4 * self.n, len(host) + 3 * doc_cap) + 8, dtype=torch.int64, device="cuda")
-        self.table = torch.empty((doc_cap + 1) * 4, dtype=torch.int32, device="cuda")
-        code, self.docs, self.tw, self.sb = self.stage2()
-        assert code == 0, code
-
-    def stage2(self):
-        return self.p.stage2_many_device(self.buf.data_ptr(), self.length, self.idx.data_ptr(), self.n, self.tape.data_ptr(), self.tape.numel(), self.sbuf.data_ptr(),
-                                         self.sbuf.numel(), self.table.data_ptr(), self.table.numel() // 4, stream=self.s)
+def resident(host, doc_cap):
+    """a host buffer's tapes (one per document) on the device, with a parser of its own"""
+    R = capi.ResidentStream(capi.DomParserImplementation(len(host) + 64), host, doc_cap=doc_cap)
+    assert R.code == 0, R.code
+    return R
 
 
 def roads(R, torch, paths):
     """-> (narrow, wide, matches): the two calls into outputs of the size a first call asked for, compared bit for bit once"""
     cells = len(paths) * R.docs
-    args = (R.tape.data_ptr(), R.tw, R.sbuf.data_ptr(), R.sb, R.table.data_ptr(), R.docs, paths)
+    args = (*R.args(), paths)
     rc, matches = R.p.at_paths_device(*args, torch.empty(cells + 1, dtype=torch.int32, device="cuda").data_ptr(), torch.empty(cells, dtype=torch.uint8, device="cuda").data_ptr(),
-                                      0, 0, 0, R.s)
-    assert rc in (0, -5), rc
+                                      0, 0, 0, R.stream)
+    assert rc in (0, capi.SJGPU_E_OVERFLOW), rc
     outs, fns = [], []
     for call in (R.p.at_paths_device, R.p.at_paths_wide_device):
         out = (torch.zeros(cells + 1, dtype=torch.int32, device="cuda"), torch.zeros(cells, dtype=torch.uint8, device="cuda"),
                torch.zeros(max(matches, 1), dtype=torch.int64, device="cuda"), torch.zeros(max(matches, 1), dtype=torch.uint8, device="cuda"))
 
         def run(call=call, out=out):
-            rc, m = call(*args, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), matches, R.s)
+            rc, m = call(*args, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), matches, R.stream)
             assert (rc, m) == (0, matches), (rc, m)
         run()
         outs.append(out)
@@ -114,7 +96,7 @@ def main():
     out = {"reps": args.reps, "unit": "ms", "cases": []}
     for mib in args.twitter_mib:
         host, statuses = corpus.twitter_like(mib << 20, 7)
-        R = Resident(torch, host, 1)
+        R = resident(host, 1)
         assert R.docs == 1
         for path in TWITTER_PATHS:
             narrow, wide, matches = roads(R, torch, [path])
@@ -129,7 +111,7 @@ def main():
         torch.cuda.empty_cache()
     if args.mib:
         host, lines = corpus.amazon_ndjson(args.mib << 20, 7)
-        R = Resident(torch, host, lines + 1)
+        R = resident(host, lines + 1)
         assert R.docs == lines
         narrow, wide, matches = roads(R, torch, [b"$[*]"])
         case = {"corpus": "amazon-like NDJSON", "mib": round(len(host) / 2 ** 20, 1), "tape_words": int(R.tw), "records": int(R.docs), "path": "$[*]", "matches": int(matches)}

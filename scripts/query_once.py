@@ -16,8 +16,6 @@ import os
 import statistics
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from simdjson_amd import build, capi, corpus  # noqa: E402
 
@@ -34,30 +32,17 @@ def main():
     build.build_sjgpu()
     host, lines = corpus.amazon_ndjson(args.mib << 20, 7)
     p = capi.DomParserImplementation(len(host) + 64)
-    s = torch.cuda.current_stream().cuda_stream
-    buf = torch.from_numpy(np.concatenate([host, np.zeros(64, np.uint8)])).cuda()
-    idx = torch.zeros(len(host) + 16, dtype=torch.int32, device="cuda")
-    assert p.stage1_device(buf.data_ptr(), len(host), idx.data_ptr(), len(host) + 3, s) == 0
-    n, flags, _ = p.result(s)
-    assert flags == 0, flags
-    sbuf_cap = 5 * (len(host) // 3) + 256
-    sbuf = torch.empty(sbuf_cap, dtype=torch.uint8, device="cuda")
-    tape_cap = min(4 * n, len(host) + 3 * (lines + 1)) + 8
-    tape = torch.empty(tape_cap, dtype=torch.int64, device="cuda")
-    table = torch.empty((lines + 2) * 4, dtype=torch.int32, device="cuda")
-
-    def run_many():
-        return p.stage2_many_device(buf.data_ptr(), len(host), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf_cap, table.data_ptr(), lines + 2, stream=s)
-
-    code, docs, tw, sb = run_many()
-    assert (code, docs) == (0, lines), (code, docs, lines)
+    R = capi.ResidentStream(p, host, doc_cap=lines + 1)
+    assert (R.code, R.docs) == (0, lines), (R.code, R.docs, lines)
+    s, n, sbuf, docs, tw, sb = R.stream, R.n, R.sbuf, R.docs, R.tw, R.sb
+    run_many = R.stage2
     top = [b"/%d" % k for k in range(8)]
     deep = [b"/%d/x/y" % k for k in range(8)]
     values = torch.empty((8, docs), dtype=torch.int64, device="cuda")
     tags = torch.empty((8, docs), dtype=torch.uint8, device="cuda")
 
     def run_pointers(pointers):
-        rc = p.at_pointers_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, pointers, values.data_ptr(), tags.data_ptr(), s)
+        rc = p.at_pointers_device(*R.args(), pointers, values.data_ptr(), tags.data_ptr(), s)
         assert rc == 0, rc
 
     run_pointers(deep)

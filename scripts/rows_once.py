@@ -26,28 +26,6 @@ POINTERS = [b"/id", b"/text", b"/user/id", b"/user/name", b"/user/followers_coun
 HEADER, TRAILER = b'{\n  "statuses": [\n', b'\n  ],\n  "search_metadata": { "count": 100, "since_id": 0 }\n}\n'
 
 
-class Resident:
-    """a host buffer's stage 1 and its tapes (one per document), everything on the device"""
-
-    def __init__(self, torch, p, host, doc_cap):
-        self.s = s = torch.cuda.current_stream().cuda_stream
-        buf = torch.from_numpy(np.concatenate([host, np.zeros(64, np.uint8)])).cuda()
-        idx = torch.zeros(len(host) + 16, dtype=torch.int32, device="cuda")
-        assert p.stage1_device(buf.data_ptr(), len(host), idx.data_ptr(), len(host) + 3, s) == 0
-        n, flags, _ = p.result(s)
-        assert flags == 0, flags
-        self.sbuf = torch.empty(5 * (len(host) // 3) + 256, dtype=torch.uint8, device="cuda")
-        self.tape = torch.empty(min(4 * n, len(host) + 3 * doc_cap) + 8, dtype=torch.int64, device="cuda")
-        self.table = torch.empty((doc_cap + 1) * 4, dtype=torch.int32, device="cuda")
-        code, self.docs, self.tw, self.sb = p.stage2_many_device(buf.data_ptr(), len(host), idx.data_ptr(), n, self.tape.data_ptr(), self.tape.numel(), self.sbuf.data_ptr(),
-                                                                 self.sbuf.numel(), self.table.data_ptr(), doc_cap + 1, stream=s)
-        assert code == 0, code
-        self.tokens = n
-
-    def args(self):
-        return self.tape.data_ptr(), self.tw, self.sbuf.data_ptr(), self.sb, self.table.data_ptr(), self.docs
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=256)
@@ -65,10 +43,10 @@ def main():
     records = np.frombuffer(raw[len(HEADER): len(raw) - len(TRAILER)].replace(b"\n    },\n", b"\n    } \n"), np.uint8)  # (no raw newline inside a string: the pattern is a record's end)
     del raw
     p = capi.DomParserImplementation(len(host) + 64)
-    D = Resident(torch, p, host, 1)
-    S = Resident(torch, p, records, statuses + 1)
-    assert (D.docs, S.docs) == (1, statuses), (D.docs, S.docs, statuses)
-    s = D.s
+    D = capi.ResidentStream(p, host, doc_cap=1)
+    S = capi.ResidentStream(p, records, doc_cap=statuses + 1)
+    assert (D.code, D.docs, S.code, S.docs) == (0, 1, 0, statuses), (D.code, D.docs, S.code, S.docs, statuses)
+    s = D.stream
     K = len(POINTERS)
     # the rows of $.statuses[*]: every record's cell, in order
     offsets = torch.empty(2, dtype=torch.int32, device="cuda")

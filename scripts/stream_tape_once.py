@@ -45,33 +45,18 @@ def main():
     broken_host[-2] = ord("}")  # the last record's closing bracket is of the wrong kind: TAPE_ERROR at that token, every string still valid
 
     p = capi.DomParserImplementation(len(array_host) + 64)
-    s = torch.cuda.current_stream().cuda_stream
-
-    def resident(a):
-        buf = torch.from_numpy(np.concatenate([a, np.zeros(64, np.uint8)])).cuda()
-        idx = torch.zeros(len(a) + 16, dtype=torch.int32, device="cuda")
-        assert p.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, s) == 0
-        n, flags, _ = p.result(s)
-        assert flags == 0, flags
-        return buf, idx, n
-
-    sbuf_cap = 5 * (len(array_host) // 3) + 256
-    sbuf = torch.empty(sbuf_cap, dtype=torch.uint8, device="cuda")
-    b_stream, i_stream, n_stream = resident(stream_host)
-    b_array, i_array, n_array = resident(array_host)
-    b_broken, i_broken, n_broken = resident(broken_host)
-    tape_cap = min(4 * n_stream, len(stream_host) + 3 * (lines + 1)) + 8
-    tape = torch.empty(max(tape_cap, len(array_host) + 8), dtype=torch.int64, device="cuda")
-    table = torch.empty((lines + 2) * 4, dtype=torch.int32, device="cuda")
-
-    def run_many(buf=b_stream, idx=i_stream, n=n_stream, length=len(stream_host)):
-        return p.stage2_many_device(buf.data_ptr(), length, idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf_cap, table.data_ptr(), lines + 2, stream=s)
+    # three resident buffers, each with its tapes; the array's (one document to the stream call) are only what stage 1 leaves for the single document's call below
+    S = capi.ResidentStream(p, stream_host, doc_cap=lines + 1)
+    A = capi.ResidentStream(p, array_host, doc_cap=1)
+    B = capi.ResidentStream(p, broken_host, doc_cap=lines + 1)
+    assert (S.code, A.code) == (0, 0), (S.code, A.code)
+    n_stream, n_array = S.n, A.n
+    single_tape = torch.empty(len(array_host) + 8, dtype=torch.int64, device="cuda")
+    run_many, run_broken = S.stage2, B.stage2
 
     def run_single():
-        return p.stage2_device(b_array.data_ptr(), len(array_host), i_array.data_ptr(), n_array, tape.data_ptr(), len(array_host) + 8, sbuf.data_ptr(), sbuf_cap, stream=s)
-
-    def run_broken():
-        return run_many(b_broken, i_broken, n_broken, len(broken_host))
+        return p.stage2_device(A.buf.data_ptr(), len(array_host), A.idx.data_ptr(), n_array, single_tape.data_ptr(), len(array_host) + 8, A.sbuf.data_ptr(), A.sbuf.numel(),
+                               stream=A.stream)
 
     # the two roads deliver the same words: an array adds its two brackets to the records' words, a stream two root words per record
     code, docs, tw_many, sb_many = run_many()

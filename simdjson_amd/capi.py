@@ -73,6 +73,7 @@ CAST_EXPORTS = ["sjgpu_cell_kinds_device", "sjgpu_cast_cells_device"]
 # SJGPU_GET_*: the getter a row of sjgpu_cast_cells_device asks of its cells
 GET_INT64, GET_UINT64, GET_DOUBLE, GET_BOOL, GET_STRING, GET_ARRAY, GET_OBJECT = 1, 2, 3, 4, 5, 6, 7
 NUMBER_OUT_OF_RANGE = 18  # what get_int64 answers a u cell, get_uint64 a negative l
+SJGPU_E_OVERFLOW = -5  # (include/sjgpu.h) an output was too small; the calls with a capacity report the one they need beside it
 
 
 def infer_getters(kinds):
@@ -272,6 +273,76 @@ def _as_u8(data):
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data, dtype=np.uint8)
     return np.frombuffer(bytes(data), dtype=np.uint8).copy() if len(data) else np.zeros(0, np.uint8)
+
+
+def strbuf_bytes(length):
+    """the string buffer that `length` bytes of JSON can need (include/sjgpu.h, sjgpu_stage2_device)"""
+    return 5 * (length // 3) + 256
+
+
+def _blob(items):
+    """A list of bytes as the C-ABI takes one (names, JSON pointers, paths) -> (the bytes back to back as a char pointer, their lengths as a pointer to uint32 or None
+    when there are none, the count).  The two pointers are ctypes objects that keep what they point into alive: hold them for the call, no longer (the calls copy)."""
+    lens = np.array([len(x) for x in items], dtype=np.uint32)
+    return ctypes.cast(ctypes.c_char_p(b"".join(items)), ctypes.c_void_p), lens.ctypes.data_as(ctypes.c_void_p) if len(lens) else None, len(items)
+
+
+def _to_capacity(call, cap):
+    """call(cap) -> (rc, needed, outputs), the outputs allocated for `cap` by the call itself.  At most two calls: a second one, with the capacity the first
+    reported, only after SJGPU_E_OVERFLOW.  -> what the last call returned"""
+    rc, needed, outputs = call(cap)
+    if rc == SJGPU_E_OVERFLOW:
+        rc, needed, outputs = call(needed)
+    return rc, needed, outputs
+
+
+def _refused(name, rc):
+    if rc:
+        raise SjgpuError(f"{name} refused its arguments ({rc})")
+
+
+class ResidentStream:
+    """A host buffer's way to resident tapes, the steps every *_many call begins with: upload, stage 1, sjgpu_stage2_many_device, everything on the parser's device
+    and on torch's current stream (`stream`).  Holds the tensors buf, idx, tape, sbuf, table -- keep the object for as long as anything enqueued may read them --
+    and n (tokens), code, docs, tw (tape words), sb (string bytes).  doc_cap: the documents to make room for, by default n (a document has a token).
+    Nothing to query leaves docs == 0: an empty buffer (code EMPTY, no tensor), a stage-1 error (that code; buf and idx only), a broken first document (its code).
+    The capacities are the contract of include/sjgpu_stream.h, and this is the one place that spells them."""
+    PADDING = 64  # slack behind the buffer: the kernels may read it and never depend on it
+
+    def __init__(self, parser, data, max_depth=1024, doc_cap=None):
+        import torch
+        a = _as_u8(data)
+        self.p, self.length, self.max_depth = parser, len(a), max_depth
+        self.code, self.docs, self.n, self.tw, self.sb = EMPTY, 0, 0, 0, 0
+        if len(a) == 0:
+            return
+        self.dev = dev = torch.device("cuda", parser.device)
+        self._stream = torch.cuda.current_stream(dev)
+        self.stream = self._stream.cuda_stream
+        self.buf = torch.from_numpy(np.concatenate([a, np.zeros(self.PADDING, np.uint8)])).to(dev)
+        self.idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
+        rc = parser.stage1_device(self.buf.data_ptr(), len(a), self.idx.data_ptr(), len(a) + 3, self.stream)
+        self.n, flags, _ = parser.result(self.stream)
+        self.code = rc or stage1_error_from_flags(self.n, flags)
+        if self.code:
+            return
+        doc_cap = self.n if doc_cap is None else doc_cap
+        self.tape = torch.empty(min(4 * self.n, len(a) + 3 * doc_cap) + 8, dtype=torch.int64, device=dev)
+        self.sbuf = torch.empty(strbuf_bytes(len(a)), dtype=torch.uint8, device=dev)
+        self.table = torch.empty((doc_cap + 1) * 4, dtype=torch.int32, device=dev)
+        self.code, self.docs, self.tw, self.sb = self.stage2()
+
+    def stage2(self):
+        """sjgpu_stage2_many_device over the same buffers, once more -> (code, docs, tape words, string bytes)"""
+        return self.p.stage2_many_device(self.buf.data_ptr(), self.length, self.idx.data_ptr(), self.n, self.tape.data_ptr(), self.tape.numel(), self.sbuf.data_ptr(),
+                                         self.sbuf.numel(), self.table.data_ptr(), self.table.numel() // 4, self.max_depth, self.stream)
+
+    def args(self):
+        """the six arguments every query call begins with"""
+        return self.tape.data_ptr(), self.tw, self.sbuf.data_ptr(), self.sb, self.table.data_ptr(), self.docs
+
+    def synchronize(self):
+        self._stream.synchronize()
 
 
 class DomParserImplementation:
@@ -478,11 +549,8 @@ class DomParserImplementation:
 
     def match_keys_device(self, buf_ptr, length, idx_ptr, n, names, match_ptr, stream=0):
         """sjgpu_match_keys_device: names = list of bytes; match_ptr -> n uint32 on the device.  Returns the number of matching keys."""
-        blob = b"".join(names)
-        lens = np.array([len(x) for x in names], dtype=np.uint32)
         m = ctypes.c_uint32(0)
-        rc = self.L.sjgpu_match_keys_device(self.h, buf_ptr, int(length), idx_ptr, int(n), ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data,
-                                            len(names), match_ptr, stream or None, ctypes.byref(m))
+        rc = self.L.sjgpu_match_keys_device(self.h, buf_ptr, int(length), idx_ptr, int(n), *_blob(names), match_ptr, stream or None, ctypes.byref(m))
         if rc != 0:
             raise SjgpuError(f"sjgpu_match_keys_device error {rc}: {self.last_error()}")
         return int(m.value)
@@ -501,7 +569,7 @@ class DomParserImplementation:
         """dom_parser_implementation::parse for a host buffer: (error_code, tape as uint64 array, string_buf as uint8 array)"""
         a = _as_u8(data)
         tape = np.zeros(len(a) + 8, dtype=np.uint64)
-        sbuf = np.zeros(5 * (len(a) // 3) + 256, dtype=np.uint8)
+        sbuf = np.zeros(strbuf_bytes(len(a)), dtype=np.uint8)
         tw, sb = ctypes.c_uint64(0), ctypes.c_uint64(0)
         rc = self.L.sjgpu_parse(self.h, a.ctypes.data if len(a) else None, len(a), int(max_depth), tape.ctypes.data, len(tape), sbuf.ctypes.data, len(sbuf),
                                 ctypes.byref(tw), ctypes.byref(sb))
@@ -524,7 +592,7 @@ class DomParserImplementation:
         [(tape, string_buf) views per document], the raw arrays (tape, string_buf, table as a DOC_SPAN array of documents + 1 entries))"""
         a = _as_u8(data)
         tape = np.zeros(4 * len(a) + 8, dtype=np.uint64)  # (4 words per token always suffice, and a token is at least one byte)
-        sbuf = np.zeros(5 * (len(a) // 3) + 256, dtype=np.uint8)
+        sbuf = np.zeros(strbuf_bytes(len(a)), dtype=np.uint8)
         table = np.zeros(len(a) + 2, dtype=DOC_SPAN)
         docs, tw, sb = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
         rc = self.L.sjgpu_parse_many(self.h, a.ctypes.data if len(a) else None, len(a), int(max_depth), tape.ctypes.data, len(tape), sbuf.ctypes.data, len(sbuf),
@@ -540,13 +608,13 @@ class DomParserImplementation:
     def at_pointers_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, pointers, value_ptr, tag_ptr, stream=0):
         """sjgpu_at_pointers_device: pointers = list of bytes (JSON pointers); value_ptr -> len(pointers) * docs uint64, tag_ptr -> as many bytes, row k = pointer k.
         Only enqueues the walk.  -> 0 or a negative SJGPU_E_* for arguments the call refuses (raises on HIP errors)"""
-        blob = b"".join(pointers)
-        lens = np.array([len(x) for x in pointers], dtype=np.uint32)
-        rc = self.L.sjgpu_at_pointers_device(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs),
-                                             ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(pointers), value_ptr, tag_ptr,
-                                             stream or None)
+        return self._raise_infra("sjgpu_at_pointers_device", self.L.sjgpu_at_pointers_device(
+            self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs), *_blob(pointers), value_ptr, tag_ptr, stream or None))
+
+    def _raise_infra(self, name, rc):
+        """-> rc, unless it is SJGPU_E_HIP or SJGPU_E_NOMEM: those are nobody's to handle"""
         if rc in (-2, -3):
-            raise SjgpuError(f"sjgpu_at_pointers_device error {rc}: {self.last_error()}")
+            raise SjgpuError(f"{name} error {rc}: {self.last_error()}")
         return rc
 
     def gather_strings_device(self, strbuf_ptr, strbuf_bytes, value_row_ptr, tag_row_ptr, docs, offsets_ptr, chars_ptr, chars_cap, stream=0):
@@ -554,43 +622,21 @@ class DomParserImplementation:
         total = ctypes.c_uint64(0)
         rc = self.L.sjgpu_gather_strings_device(self.h, strbuf_ptr, int(strbuf_bytes), value_row_ptr, tag_row_ptr, int(docs), offsets_ptr, chars_ptr or None, int(chars_cap),
                                                 stream or None, ctypes.byref(total))
-        if rc in (-2, -3):
-            raise SjgpuError(f"sjgpu_gather_strings_device error {rc}: {self.last_error()}")
-        return rc, int(total.value)
+        return self._raise_infra("sjgpu_gather_strings_device", rc), int(total.value)
 
     def extract_many(self, data, pointers, max_depth=1024):
         """Field X of every record as a column: upload, stage 1, sjgpu_stage2_many_device and sjgpu_at_pointers_device with everything resident; only the columns come back.
         -> (error_code of the first broken document or 0, documents delivered, tags uint8[K, docs], values uint64[K, docs])"""
         import torch
-        a = _as_u8(data)
         K = len(pointers)
-        empty = (np.zeros((K, 0), np.uint8), np.zeros((K, 0), np.uint64))
-        if len(a) == 0:
-            return (EMPTY, 0) + empty
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        buf = torch.from_numpy(np.concatenate([a, np.zeros(16, np.uint8)])).to(dev)
-        idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
-        rc = self.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, stream)
-        n, flags, _ = self.result(stream)
-        e1 = stage1_error_from_flags(n, flags)
-        if rc or e1:
-            return (rc or e1, 0) + empty
-        tape_cap = min(4 * n, len(a) + 3 * n) + 8
-        tape = torch.empty(tape_cap, dtype=torch.int64, device=dev)
-        sbuf = torch.empty(5 * (len(a) // 3) + 256, dtype=torch.uint8, device=dev)
-        table = torch.empty((n + 1) * 4, dtype=torch.int32, device=dev)
-        code, docs, tw, sb = self.stage2_many_device(buf.data_ptr(), len(a), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf.numel(), table.data_ptr(), n + 1,
-                                                     max_depth, stream)
-        if docs == 0 or K == 0:
-            return (code, docs, np.zeros((K, docs), np.uint8), np.zeros((K, docs), np.uint64))
-        values = torch.empty((K, docs), dtype=torch.int64, device=dev)
-        tags = torch.empty((K, docs), dtype=torch.uint8, device=dev)
-        rc = self.at_pointers_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, pointers, values.data_ptr(), tags.data_ptr(), stream)
-        if rc:
-            raise SjgpuError(f"sjgpu_at_pointers_device refused its arguments ({rc})")
-        torch.cuda.current_stream(dev).synchronize()
-        return code, docs, tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
+        S = ResidentStream(self, data, max_depth)
+        if S.docs == 0 or K == 0:
+            return S.code, S.docs, np.zeros((K, S.docs), np.uint8), np.zeros((K, S.docs), np.uint64)
+        values = torch.empty((K, S.docs), dtype=torch.int64, device=S.dev)
+        tags = torch.empty((K, S.docs), dtype=torch.uint8, device=S.dev)
+        _refused("sjgpu_at_pointers_device", self.at_pointers_device(*S.args(), pointers, values.data_ptr(), tags.data_ptr(), S.stream))
+        S.synchronize()
+        return S.code, S.docs, tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
 
     def at_paths_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap, stream=0):
         """sjgpu_at_paths_device: paths = list of bytes (JSONPath, wildcards allowed); offsets_ptr -> len(paths) * docs + 1 uint32, status_ptr -> len(paths) * docs bytes,
@@ -605,16 +651,30 @@ class DomParserImplementation:
 
     def _at_paths(self, name, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, paths, offsets_ptr, status_ptr, value_ptr, tag_ptr, match_cap, stream, roots=()):
         """roots: (root_value_ptr, root_tag_ptr, rows) for the call rooted at cells, which takes them behind docs"""
-        blob = b"".join(paths)
-        lens = np.array([len(x) for x in paths], dtype=np.uint32)
         matches = ctypes.c_uint64(0)
         roots = (roots[0] or None, roots[1] or None, int(roots[2])) if roots else ()
-        rc = getattr(self.L, name)(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs), *roots,
-                                   ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(paths), offsets_ptr, status_ptr or None,
+        rc = getattr(self.L, name)(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs), *roots, *_blob(paths), offsets_ptr, status_ptr or None,
                                    value_ptr or None, tag_ptr or None, int(match_cap), stream or None, ctypes.byref(matches))
-        if rc in (-2, -3):
-            raise SjgpuError(f"{name} error {rc}: {self.last_error()}")
-        return rc, int(matches.value)
+        return self._raise_infra(name, rc), int(matches.value)
+
+    def _matches(self, name, S, paths, offsets, status, cap, roots=()):
+        """one call of a paths entry point over the tapes of S, into values / tags it allocates for cap matches: the `call` of _to_capacity -> (rc, matches, (values, tags))"""
+        import torch
+        values = torch.empty(max(cap, 1), dtype=torch.int64, device=S.dev)
+        tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=S.dev)
+        rc, matches = self._at_paths(name, *S.args(), paths, offsets.data_ptr(), status.data_ptr(), values.data_ptr(), tags.data_ptr(), cap, S.stream, roots)
+        return rc, matches, (values, tags)
+
+    def _rows_of(self, S, row_path, wide):
+        """the rows of a table: the matches of row_path in the documents of S, ONE call with K = 1 (wide: of sjgpu_at_paths_wide_device), repeated once at the capacity it
+        reported -> (row_offsets int32[docs + 1], row_status uint8[docs], root_values int64[>= rows], root_tags uint8[>= rows], rows), tensors of the device, enqueued only"""
+        import torch
+        row_offsets = torch.empty(S.docs + 1, dtype=torch.int32, device=S.dev)
+        row_status = torch.empty(S.docs, dtype=torch.uint8, device=S.dev)
+        name = "sjgpu_at_paths_wide_device" if wide else "sjgpu_at_paths_device"
+        rc, rows, (root_values, root_tags) = _to_capacity(lambda cap: self._matches(name, S, [row_path], row_offsets, row_status, cap), int(S.tw // 8 + 1))
+        _refused(name, rc)
+        return row_offsets, row_status, root_values, root_tags, rows
 
     def explode_many(self, data, paths, max_depth=1024, first_cap=None, wide=False):
         """The arrays of every record as one ragged column: upload, stage 1, sjgpu_stage2_many_device and sjgpu_at_paths_device with everything resident (the twin of
@@ -622,60 +682,26 @@ class DomParserImplementation:
         match per tape word in eight).  wide: sjgpu_at_paths_wide_device in its place (the same column; the choice is the caller's).
         -> (error_code of the first broken document or 0, documents delivered, status uint8[K, docs], offsets uint32[K * docs + 1], tags uint8[matches], values uint64[matches])"""
         import torch
-        a = _as_u8(data)
         K = len(paths)
-
-        def nothing(code, docs):
-            return code, docs, np.zeros((K, docs), np.uint8), np.zeros(K * docs + 1, np.uint32), np.zeros(0, np.uint8), np.zeros(0, np.uint64)
-        if len(a) == 0:
-            return nothing(EMPTY, 0)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        buf = torch.from_numpy(np.concatenate([a, np.zeros(16, np.uint8)])).to(dev)
-        idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
-        rc = self.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, stream)
-        n, flags, _ = self.result(stream)
-        e1 = stage1_error_from_flags(n, flags)
-        if rc or e1:
-            return nothing(rc or e1, 0)
-        tape_cap = min(4 * n, len(a) + 3 * n) + 8
-        tape = torch.empty(tape_cap, dtype=torch.int64, device=dev)
-        sbuf = torch.empty(5 * (len(a) // 3) + 256, dtype=torch.uint8, device=dev)
-        table = torch.empty((n + 1) * 4, dtype=torch.int32, device=dev)
-        code, docs, tw, sb = self.stage2_many_device(buf.data_ptr(), len(a), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf.numel(), table.data_ptr(), n + 1,
-                                                     max_depth, stream)
-        if docs == 0 or K == 0:
-            return nothing(code, docs)
-        offsets = torch.empty(K * docs + 1, dtype=torch.int32, device=dev)
-        status = torch.empty((K, docs), dtype=torch.uint8, device=dev)
-        cap = int(tw // 8 + 1 if first_cap is None else first_cap)
-        at_paths = self.at_paths_wide_device if wide else self.at_paths_device
-        for attempt in range(2):
-            values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-            tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            rc, matches = at_paths(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, paths, offsets.data_ptr(), status.data_ptr(), values.data_ptr(),
-                                   tags.data_ptr(), cap, stream)
-            if rc != -5:  # SJGPU_E_OVERFLOW: once more, with what it asks for
-                break
-            cap = matches
-        if rc:
-            raise SjgpuError(f"sjgpu_at_paths{'_wide' if wide else ''}_device refused its arguments ({rc})")
-        torch.cuda.current_stream(dev).synchronize()
-        return code, docs, status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(), values[:matches].cpu().numpy().view(np.uint64)
+        S = ResidentStream(self, data, max_depth)
+        if S.docs == 0 or K == 0:
+            return S.code, S.docs, np.zeros((K, S.docs), np.uint8), np.zeros(K * S.docs + 1, np.uint32), np.zeros(0, np.uint8), np.zeros(0, np.uint64)
+        offsets = torch.empty(K * S.docs + 1, dtype=torch.int32, device=S.dev)
+        status = torch.empty((K, S.docs), dtype=torch.uint8, device=S.dev)
+        name = "sjgpu_at_paths_wide_device" if wide else "sjgpu_at_paths_device"
+        rc, matches, (values, tags) = _to_capacity(lambda cap: self._matches(name, S, paths, offsets, status, cap), int(S.tw // 8 + 1 if first_cap is None else first_cap))
+        _refused(name, rc)
+        S.synchronize()
+        return S.code, S.docs, status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(), values[:matches].cpu().numpy().view(np.uint64)
 
     def at_pointers_from_cells_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, root_value_ptr, root_tag_ptr, rows, pointers, value_ptr, tag_ptr,
                                       stream=0):
         """sjgpu_at_pointers_from_cells_device: at_pointer rooted at the `rows` cells root_value_ptr / root_tag_ptr (a row of at_pointers_device's output, the matches of
         at_paths_device, a row of this call's own); pointers = list of bytes; value_ptr -> len(pointers) * rows uint64, tag_ptr -> as many bytes, row k = pointer k.
         Only enqueues the walk.  -> 0 or a negative SJGPU_E_* for arguments the call refuses (raises on HIP errors and on memory the context could not get)"""
-        blob = b"".join(pointers)
-        lens = np.array([len(x) for x in pointers], dtype=np.uint32)
-        rc = self.L.sjgpu_at_pointers_from_cells_device(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs), root_value_ptr, root_tag_ptr,
-                                                        int(rows), ctypes.cast(ctypes.c_char_p(blob), ctypes.c_void_p), lens.ctypes.data if len(lens) else None, len(pointers),
-                                                        value_ptr, tag_ptr, stream or None)
-        if rc in (-2, -3):
-            raise SjgpuError(f"sjgpu_at_pointers_from_cells_device error {rc}: {self.last_error()}")
-        return rc
+        return self._raise_infra("sjgpu_at_pointers_from_cells_device", self.L.sjgpu_at_pointers_from_cells_device(
+            self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs), root_value_ptr, root_tag_ptr, int(rows), *_blob(pointers), value_ptr, tag_ptr,
+            stream or None))
 
     def table_many(self, data, row_path, pointers, max_depth=1024, wide=False):
         """One row per match of row_path, one column per pointer: upload, stage 1, sjgpu_stage2_many_device, ONE sjgpu_at_paths_device call with K = 1 (wide:
@@ -691,53 +717,18 @@ class DomParserImplementation:
         """table_many's work with the table left on the device -> (code, docs, row_offsets int32[docs + 1], tags uint8[K, rows], values int64[K, rows], (string buffer,
         its bytes)), all torch tensors of the device, complete (the stream has been waited for); (code, 0, None, None, None, None) when no document was delivered"""
         import torch
-        a = _as_u8(data)
         K = len(pointers)
-
-        def nothing(code, docs):
-            return code, docs, None, None, None, None
-        if len(a) == 0:
-            return nothing(EMPTY, 0)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        buf = torch.from_numpy(np.concatenate([a, np.zeros(16, np.uint8)])).to(dev)
-        idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
-        rc = self.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, stream)
-        n, flags, _ = self.result(stream)
-        e1 = stage1_error_from_flags(n, flags)
-        if rc or e1:
-            return nothing(rc or e1, 0)
-        tape_cap = min(4 * n, len(a) + 3 * n) + 8
-        tape = torch.empty(tape_cap, dtype=torch.int64, device=dev)
-        sbuf = torch.empty(5 * (len(a) // 3) + 256, dtype=torch.uint8, device=dev)
-        table = torch.empty((n + 1) * 4, dtype=torch.int32, device=dev)
-        code, docs, tw, sb = self.stage2_many_device(buf.data_ptr(), len(a), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf.numel(), table.data_ptr(), n + 1,
-                                                     max_depth, stream)
-        if docs == 0:
-            return nothing(code, 0)
-        offsets = torch.empty(docs + 1, dtype=torch.int32, device=dev)
-        status = torch.empty(docs, dtype=torch.uint8, device=dev)
-        cap = int(tw // 8 + 1)
-        at_paths = self.at_paths_wide_device if wide else self.at_paths_device
-        for attempt in range(2):
-            root_values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-            root_tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            rc, rows = at_paths(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, [row_path], offsets.data_ptr(), status.data_ptr(), root_values.data_ptr(),
-                                root_tags.data_ptr(), cap, stream)
-            if rc != -5:  # SJGPU_E_OVERFLOW: once more, with what it asks for
-                break
-            cap = rows
-        if rc:
-            raise SjgpuError(f"sjgpu_at_paths{'_wide' if wide else ''}_device refused its arguments ({rc})")
-        values = torch.empty((K, rows), dtype=torch.int64, device=dev)
-        tags = torch.empty((K, rows), dtype=torch.uint8, device=dev)
+        S = ResidentStream(self, data, max_depth)
+        if S.docs == 0:
+            return S.code, 0, None, None, None, None
+        offsets, status, root_values, root_tags, rows = self._rows_of(S, row_path, wide)
+        values = torch.empty((K, rows), dtype=torch.int64, device=S.dev)
+        tags = torch.empty((K, rows), dtype=torch.uint8, device=S.dev)
         if K and rows:
-            rc = self.at_pointers_from_cells_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, root_values.data_ptr(), root_tags.data_ptr(), rows, pointers,
-                                                    values.data_ptr(), tags.data_ptr(), stream)
-            if rc:
-                raise SjgpuError(f"sjgpu_at_pointers_from_cells_device refused its arguments ({rc})")
-        torch.cuda.current_stream(dev).synchronize()
-        return code, docs, offsets, tags, values, (sbuf, sb)
+            _refused("sjgpu_at_pointers_from_cells_device", self.at_pointers_from_cells_device(*S.args(), root_values.data_ptr(), root_tags.data_ptr(), rows, pointers,
+                                                                                               values.data_ptr(), tags.data_ptr(), S.stream))
+        S.synchronize()  # (S, status and the roots live until here: the walks read them)
+        return S.code, S.docs, offsets, tags, values, (S.sbuf, S.sb)
 
     def at_paths_from_cells_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, root_value_ptr, root_tag_ptr, rows, paths, offsets_ptr, status_ptr,
                                    value_ptr, tag_ptr, match_cap, stream=0):
@@ -755,68 +746,25 @@ class DomParserImplementation:
         -> (error_code of the first broken document or 0, documents delivered, row_offsets uint32[docs + 1], status uint8[K, rows], offsets uint32[K * rows + 1],
         tags uint8[matches], values uint64[matches])"""
         import torch
-        a = _as_u8(data)
         K = len(paths)
-
-        def nothing(code, docs):
-            return code, docs, np.zeros(docs + 1, np.uint32), np.zeros((K, 0), np.uint8), np.zeros(1, np.uint32), np.zeros(0, np.uint8), np.zeros(0, np.uint64)
-        if len(a) == 0:
-            return nothing(EMPTY, 0)
-        dev = torch.device("cuda", self.device)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        buf = torch.from_numpy(np.concatenate([a, np.zeros(16, np.uint8)])).to(dev)
-        idx = torch.empty(len(a) + 16, dtype=torch.int32, device=dev)
-        rc = self.stage1_device(buf.data_ptr(), len(a), idx.data_ptr(), len(a) + 3, stream)
-        n, flags, _ = self.result(stream)
-        e1 = stage1_error_from_flags(n, flags)
-        if rc or e1:
-            return nothing(rc or e1, 0)
-        tape_cap = min(4 * n, len(a) + 3 * n) + 8
-        tape = torch.empty(tape_cap, dtype=torch.int64, device=dev)
-        sbuf = torch.empty(5 * (len(a) // 3) + 256, dtype=torch.uint8, device=dev)
-        table = torch.empty((n + 1) * 4, dtype=torch.int32, device=dev)
-        code, docs, tw, sb = self.stage2_many_device(buf.data_ptr(), len(a), idx.data_ptr(), n, tape.data_ptr(), tape_cap, sbuf.data_ptr(), sbuf.numel(), table.data_ptr(), n + 1,
-                                                     max_depth, stream)
-        if docs == 0:
-            return nothing(code, 0)
-        row_offsets = torch.empty(docs + 1, dtype=torch.int32, device=dev)
-        row_status = torch.empty(docs, dtype=torch.uint8, device=dev)
-        cap = int(tw // 8 + 1)
-        at_paths = self.at_paths_wide_device if wide else self.at_paths_device
-        for attempt in range(2):
-            root_values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-            root_tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            rc, rows = at_paths(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, [row_path], row_offsets.data_ptr(), row_status.data_ptr(), root_values.data_ptr(),
-                                root_tags.data_ptr(), cap, stream)
-            if rc != -5:  # SJGPU_E_OVERFLOW: once more, with what it asks for
-                break
-            cap = rows
-        if rc:
-            raise SjgpuError(f"sjgpu_at_paths{'_wide' if wide else ''}_device refused its arguments ({rc})")
-        offsets = torch.empty(K * rows + 1, dtype=torch.int32, device=dev)
-        status = torch.empty((K, rows), dtype=torch.uint8, device=dev)
-        cap = int(tw // 8 + 1 if first_cap is None else first_cap)
-        for attempt in range(2):
-            values = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-            tags = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            rc, matches = self.at_paths_from_cells_device(tape.data_ptr(), tw, sbuf.data_ptr(), sb, table.data_ptr(), docs, root_values.data_ptr(), root_tags.data_ptr(), rows, paths,
-                                                          offsets.data_ptr(), status.data_ptr(), values.data_ptr(), tags.data_ptr(), cap, stream)
-            if rc != -5:
-                break
-            cap = matches
-        if rc:
-            raise SjgpuError(f"sjgpu_at_paths_from_cells_device refused its arguments ({rc})")
-        torch.cuda.current_stream(dev).synchronize()
-        return (code, docs, row_offsets.cpu().numpy().view(np.uint32), status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(),
+        S = ResidentStream(self, data, max_depth)
+        if S.docs == 0:
+            return S.code, 0, np.zeros(1, np.uint32), np.zeros((K, 0), np.uint8), np.zeros(1, np.uint32), np.zeros(0, np.uint8), np.zeros(0, np.uint64)
+        row_offsets, row_status, root_values, root_tags, rows = self._rows_of(S, row_path, wide)
+        offsets = torch.empty(K * rows + 1, dtype=torch.int32, device=S.dev)
+        status = torch.empty((K, rows), dtype=torch.uint8, device=S.dev)
+        name, roots = "sjgpu_at_paths_from_cells_device", (root_values.data_ptr(), root_tags.data_ptr(), rows)
+        rc, matches, (values, tags) = _to_capacity(lambda cap: self._matches(name, S, paths, offsets, status, cap, roots), int(S.tw // 8 + 1 if first_cap is None else first_cap))
+        _refused(name, rc)
+        S.synchronize()
+        return (S.code, S.docs, row_offsets.cpu().numpy().view(np.uint32), status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(),
                 values[:matches].cpu().numpy().view(np.uint64))
 
     def cell_kinds_device(self, value_ptr, tag_ptr, n, K, kinds_ptr, stream=0):
         """sjgpu_cell_kinds_device: the census of K rows of n cells; kinds_ptr -> K * 16 uint32.  Only enqueues.  -> 0 or a negative SJGPU_E_* for arguments the call
         refuses (raises on HIP errors)"""
-        rc = self.L.sjgpu_cell_kinds_device(self.h, value_ptr or None, tag_ptr or None, int(n), int(K), kinds_ptr or None, stream or None)
-        if rc in (-2, -3):
-            raise SjgpuError(f"sjgpu_cell_kinds_device error {rc}: {self.last_error()}")
-        return rc
+        return self._raise_infra("sjgpu_cell_kinds_device",
+                                 self.L.sjgpu_cell_kinds_device(self.h, value_ptr or None, tag_ptr or None, int(n), int(K), kinds_ptr or None, stream or None))
 
     def cast_cells_device(self, value_ptr, tag_ptr, n, getters, value_out_ptr, code_out_ptr, valid_out_ptr, counts_out_ptr, stream=0):
         """sjgpu_cast_cells_device: row k of the K = len(getters) rows of n cells asks getters[k] (SJGPU_GET_*) of each of its cells; value_out_ptr -> K * n uint64,
@@ -825,9 +773,7 @@ class DomParserImplementation:
         g = np.array(list(getters), dtype=np.uint8)
         rc = self.L.sjgpu_cast_cells_device(self.h, value_ptr or None, tag_ptr or None, int(n), len(g), g.ctypes.data if len(g) else None, value_out_ptr or None,
                                             code_out_ptr or None, valid_out_ptr or None, counts_out_ptr or None, stream or None)
-        if rc in (-2, -3):
-            raise SjgpuError(f"sjgpu_cast_cells_device error {rc}: {self.last_error()}")
-        return rc
+        return self._raise_infra("sjgpu_cast_cells_device", rc)
 
     def typed_table_many(self, data, row_path, pointers, getters=None, wide=False, max_depth=1024):
         """table_many with typed columns: its cells stay on the device, sjgpu_cell_kinds_device takes their census, infer_getters picks a getter per column where
@@ -851,9 +797,7 @@ class DomParserImplementation:
         rows = tags.shape[1]
         kinds = torch.empty((K, 16), dtype=torch.int32, device=dev)
         if K:
-            rc = self.cell_kinds_device(values.data_ptr(), tags.data_ptr(), rows, K, kinds.data_ptr(), stream)
-            if rc:
-                raise SjgpuError(f"sjgpu_cell_kinds_device refused its arguments ({rc})")
+            _refused("sjgpu_cell_kinds_device", self.cell_kinds_device(values.data_ptr(), tags.data_ptr(), rows, K, kinds.data_ptr(), stream))
         kinds_h = kinds.cpu().numpy().view(np.uint32)
         inferred = infer_getters(kinds_h)
         picked = [inferred[k] if getters is None or not getters[k] else int(getters[k]) for k in range(K)]
@@ -869,10 +813,8 @@ class DomParserImplementation:
         out_codes = torch.empty((C, rows), dtype=torch.uint8, device=dev)
         valid = torch.empty((C, W), dtype=torch.int64, device=dev)
         counts = torch.empty((C, 4), dtype=torch.int32, device=dev)
-        rc = self.cast_cells_device(in_values.data_ptr(), in_tags.data_ptr(), rows, [picked[k] for k in cast], out_values.data_ptr(), out_codes.data_ptr(), valid.data_ptr(),
-                                    counts.data_ptr(), stream)
-        if rc:
-            raise SjgpuError(f"sjgpu_cast_cells_device refused its arguments ({rc})")
+        _refused("sjgpu_cast_cells_device", self.cast_cells_device(in_values.data_ptr(), in_tags.data_ptr(), rows, [picked[k] for k in cast], out_values.data_ptr(),
+                                                                   out_codes.data_ptr(), valid.data_ptr(), counts.data_ptr(), stream))
         sbuf, sb = strings
         gathered = {}
         for j, k in enumerate(cast):
@@ -880,12 +822,14 @@ class DomParserImplementation:
                 continue
             # a cell that is no string has code != 0 and value 0; the gather wants the tags: the valid cells of a STRING column are exactly its `"` cells
             soff = torch.empty(rows + 1, dtype=torch.int32, device=dev)
-            rc, total = self.gather_strings_device(sbuf.data_ptr(), sb, in_values[j].data_ptr(), in_tags[j].data_ptr(), rows, soff.data_ptr(), 0, 0, stream)
-            chars = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-            if rc == -5:
-                rc, total = self.gather_strings_device(sbuf.data_ptr(), sb, in_values[j].data_ptr(), in_tags[j].data_ptr(), rows, soff.data_ptr(), chars.data_ptr(), total, stream)
-            if rc:
-                raise SjgpuError(f"sjgpu_gather_strings_device refused its arguments ({rc})")
+
+            def gather(cap):  # the first call only asks: capacity 0 and no characters' address
+                chars = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+                rc, total = self.gather_strings_device(sbuf.data_ptr(), sb, in_values[j].data_ptr(), in_tags[j].data_ptr(), rows, soff.data_ptr(), chars.data_ptr() if cap else 0, cap,
+                                                       stream)
+                return rc, total, chars
+            rc, total, chars = _to_capacity(gather, 0)
+            _refused("sjgpu_gather_strings_device", rc)
             gathered[k] = (soff, chars[:total])
         torch.cuda.current_stream(dev).synchronize()
         out_h, codes_h, valid_h, counts_h = out_values.cpu().numpy(), out_codes.cpu().numpy(), valid.cpu().numpy(), counts.cpu().numpy().view(np.uint32)
