@@ -63,7 +63,7 @@ def sjgpu_source_stamp():
     h = hashlib.sha256()
     for f in [*_csrc(*SJGPU_SOURCES), *_csrc(*SJGPU_HEADERS), os.path.join(_paths.INCLUDE_DIR, "sjgpu.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_stream.h"),
               os.path.join(_paths.INCLUDE_DIR, "sjgpu_query.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_paths.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_rows.h"),
-              os.path.join(_paths.INCLUDE_DIR, "sjgpu_lists.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_cast.h")]:
+              os.path.join(_paths.INCLUDE_DIR, "sjgpu_lists.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_cast.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_fields.h")]:
         h.update(os.path.relpath(f, _paths.REPO_ROOT).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()

@@ -76,6 +76,10 @@ NUMBER_OUT_OF_RANGE = 18  # what get_int64 answers a u cell, get_uint64 a negati
 SJGPU_E_OVERFLOW = -5  # (include/sjgpu.h) an output was too small; the calls with a capacity report the one they need beside it
 
 
+# what include/sjgpu_fields.h declares (map columns over device tapes: the fields of each cell's object, keys as string cells, and the size() of each cell's container)
+FIELDS_EXPORTS = ["sjgpu_object_fields_from_cells_device", "sjgpu_cell_sizes_device"]
+
+
 def infer_getters(kinds):
     """The getter a loader would ask of each row, from its census (kinds: K x 16 counts as sjgpu_cell_kinds_device leaves them) -> list of K SJGPU_GET_* or 0.
     The ELEMENTS of a row are its cells except the nulls and the codes 17 / 19 / 20 / 22 (they become invalid bits under any getter):
@@ -209,6 +213,11 @@ def load_library():
     L.sjgpu_cell_kinds_device.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     L.sjgpu_cast_cells_device.restype = ctypes.c_int
     L.sjgpu_cast_cells_device.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.sjgpu_object_fields_from_cells_device.restype = ctypes.c_int
+    L.sjgpu_object_fields_from_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp,
+                                                        ctypes.c_uint64, vp, u64p]
+    L.sjgpu_cell_sizes_device.restype = ctypes.c_int
+    L.sjgpu_cell_sizes_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int
@@ -759,6 +768,68 @@ class DomParserImplementation:
         S.synchronize()
         return (S.code, S.docs, row_offsets.cpu().numpy().view(np.uint32), status.cpu().numpy(), offsets.cpu().numpy().view(np.uint32), tags[:matches].cpu().numpy(),
                 values[:matches].cpu().numpy().view(np.uint64))
+
+    def object_fields_from_cells_device(self, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, docs_ptr, docs, root_value_ptr, root_tag_ptr, rows, offsets_ptr, status_ptr,
+                                        key_value_ptr, key_tag_ptr, value_ptr, tag_ptr, field_cap, stream=0):
+        """sjgpu_object_fields_from_cells_device: the fields of the objects the `rows` cells root_value_ptr / root_tag_ptr describe (as for at_pointers_from_cells_device);
+        offsets_ptr -> rows + 1 uint32, status_ptr -> rows bytes, key_value_ptr / value_ptr -> field_cap uint64, key_tag_ptr / tag_ptr -> field_cap bytes.
+        -> (code, fields): 0, CAPACITY or a negative SJGPU_E_* (raises on HIP errors and on memory the context could not get)"""
+        fields = ctypes.c_uint64(0)
+        rc = self.L.sjgpu_object_fields_from_cells_device(self.h, tape_ptr, int(tape_words), strbuf_ptr, int(strbuf_bytes), docs_ptr, int(docs), root_value_ptr or None,
+                                                          root_tag_ptr or None, int(rows), offsets_ptr, status_ptr or None, key_value_ptr or None, key_tag_ptr or None,
+                                                          value_ptr or None, tag_ptr or None, int(field_cap), stream or None, ctypes.byref(fields))
+        return self._raise_infra("sjgpu_object_fields_from_cells_device", rc), int(fields.value)
+
+    def cell_sizes_device(self, tape_ptr, tape_words, docs_ptr, docs, root_value_ptr, root_tag_ptr, rows, size_ptr, code_ptr, stream=0):
+        """sjgpu_cell_sizes_device: size() of the containers the `rows` cells describe; size_ptr -> rows uint32, code_ptr -> rows bytes.  Only enqueues the launches.
+        -> 0 or a negative SJGPU_E_* for arguments the call refuses (raises on HIP errors and on memory the context could not get)"""
+        return self._raise_infra("sjgpu_cell_sizes_device", self.L.sjgpu_cell_sizes_device(
+            self.h, tape_ptr, int(tape_words), docs_ptr, int(docs), root_value_ptr or None, root_tag_ptr or None, int(rows), size_ptr or None, code_ptr or None, stream or None))
+
+    def _fields(self, S, roots, offsets, status, cap):
+        """one sjgpu_object_fields_from_cells_device over the tapes of S, into key and value rows it allocates for cap fields: the `call` of _to_capacity
+        -> (rc, fields, (key_values, key_tags, values, tags))"""
+        import torch
+        rows64 = [torch.empty(max(cap, 1), dtype=torch.int64, device=S.dev) for _ in range(2)]
+        rows8 = [torch.empty(max(cap, 1), dtype=torch.uint8, device=S.dev) for _ in range(2)]
+        rc, fields = self.object_fields_from_cells_device(*S.args(), *roots, offsets.data_ptr(), status.data_ptr(), rows64[0].data_ptr(), rows8[0].data_ptr(),
+                                                          rows64[1].data_ptr(), rows8[1].data_ptr(), cap, S.stream)
+        return rc, fields, (rows64[0], rows8[0], rows64[1], rows8[1])
+
+    def fields_many(self, data, row_path, max_depth=1024, wide=False, first_cap=None):
+        """One row per match of row_path, one MAP column: the fields of each row's object, keys and values.  Upload, stage 1, sjgpu_stage2_many_device, ONE
+        sjgpu_at_paths_device call with K = 1 (wide: sjgpu_at_paths_wide_device), sjgpu_object_fields_from_cells_device over its matches -- repeated once with the capacity
+        it reported (first_cap: its first guess, by default one field per tape word in eight) -- and ONE sjgpu_gather_strings_device over the key row, with everything
+        resident (the twin of lists_many).  Row r is match r of row_path; the rows of document d are row_offsets[d] .. row_offsets[d + 1]; the fields of row r are
+        offsets[r] .. offsets[r + 1] (a row whose status is not 0 has none), field i with the key key_chars[key_offsets[i] .. key_offsets[i + 1]).
+        -> (error_code of the first broken document or 0, documents delivered, row_offsets uint32[docs + 1], status uint8[rows], offsets uint32[rows + 1],
+        key_offsets uint32[fields + 1], key_chars uint8[...], tags uint8[fields], values uint64[fields])"""
+        import torch
+        S = ResidentStream(self, data, max_depth)
+        if S.docs == 0:
+            return (S.code, 0, np.zeros(1, np.uint32), np.zeros(0, np.uint8), np.zeros(1, np.uint32), np.zeros(1, np.uint32), np.zeros(0, np.uint8), np.zeros(0, np.uint8),
+                    np.zeros(0, np.uint64))
+        row_offsets, row_status, root_values, root_tags, rows = self._rows_of(S, row_path, wide)
+        offsets = torch.empty(rows + 1, dtype=torch.int32, device=S.dev)
+        status = torch.empty(max(rows, 1), dtype=torch.uint8, device=S.dev)
+        name, roots = "sjgpu_object_fields_from_cells_device", (root_values.data_ptr(), root_tags.data_ptr(), rows)
+        rc, fields, (key_values, key_tags, values, tags) = _to_capacity(lambda cap: self._fields(S, roots, offsets, status, cap),
+                                                                        int(S.tw // 8 + 1 if first_cap is None else first_cap))
+        _refused(name, rc)
+        key_offsets = torch.empty(fields + 1, dtype=torch.int32, device=S.dev)
+        gather = lambda cap: self._key_chars(S, key_values, key_tags, fields, key_offsets, cap)  # noqa: E731
+        rc, total, key_chars = _to_capacity(gather, int(min(S.sb, 16 * fields)))  # (distinct keys take less than the string buffer: one call, unless keys are long)
+        _refused("sjgpu_gather_strings_device", rc)
+        S.synchronize()
+        return (S.code, S.docs, row_offsets.cpu().numpy().view(np.uint32), status[:rows].cpu().numpy(), offsets.cpu().numpy().view(np.uint32),
+                key_offsets.cpu().numpy().view(np.uint32), key_chars[:total].cpu().numpy(), tags[:fields].cpu().numpy(), values[:fields].cpu().numpy().view(np.uint64))
+
+    def _key_chars(self, S, key_values, key_tags, fields, key_offsets, cap):
+        """one sjgpu_gather_strings_device over a key row, into characters it allocates for cap bytes: the `call` of _to_capacity -> (rc, bytes, chars)"""
+        import torch
+        chars = torch.empty(max(cap, 1), dtype=torch.uint8, device=S.dev)
+        rc, total = self.gather_strings_device(S.sbuf.data_ptr(), S.sb, key_values.data_ptr(), key_tags.data_ptr(), fields, key_offsets.data_ptr(), chars.data_ptr(), cap, S.stream)
+        return rc, total, chars
 
     def cell_kinds_device(self, value_ptr, tag_ptr, n, K, kinds_ptr, stream=0):
         """sjgpu_cell_kinds_device: the census of K rows of n cells; kinds_ptr -> K * 16 uint32.  Only enqueues.  -> 0 or a negative SJGPU_E_* for arguments the call

@@ -7,6 +7,7 @@
 #include "sjgpu_rows.h"
 #include "sjgpu_lists.h"
 #include "sjgpu_cast.h"
+#include "sjgpu_fields.h"
 #include "sj_path_program.h"
 
 extern "C" {
@@ -622,6 +623,106 @@ int sjgpu_at_paths_from_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint6
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s)); // (the program block, the verdicts and the workspace are free again when the call returns)
   }
+  return 0;
+}
+
+// ---- the fields and the sizes of the cells' containers (k_object_fields_count, k_object_fields_fill, k_cell_sizes in sjgpu_query.hip; include/sjgpu_fields.h) ----
+} // extern "C"
+
+namespace {
+// What the two calls do before their first kernel, behind their own null checks: the checks on the tapes, the table and the roots that
+// sjgpu_at_paths_from_cells_device makes, rows == 0, the wait for the context's previous walk, the context's block -- [0] the table check's word, [256] the roots'
+// verdicts (4 bytes per root) --, `workspace` bytes of d_tmp and the table check.  -> 0 with *done = false: the table passed; *done = true: the call is over
+int fields_begin(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, uint64_t string_bytes, const void *docs_dev, uint32_t docs, const void *root_value_dev,
+                 const void *root_tag_dev, uint32_t rows, size_t workspace, void *stream, hipStream_t *stream_out, bool *done) {
+  *done = true;
+  if (!ctx || !tape_dev || !docs_dev || (rows && (!root_value_dev || !root_tag_dev))) { return SJGPU_E_BADARG; }
+  if ((reinterpret_cast<uintptr_t>(tape_dev) & 7u) || (reinterpret_cast<uintptr_t>(root_value_dev) & 7u) || (reinterpret_cast<uintptr_t>(docs_dev) & 15u)) { return SJGPU_E_BADARG; }
+  if (tape_words > 0xFFFFFFFFull || string_bytes > 0xFFFFFFFFull || docs >= 0xFFFFFFF0u || uint64_t(rows) + 1 > 0xFFFFFFF0ull) { return SJGPU_E_BADARG; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick(ctx, stream);
+  *stream_out = s;
+  if (rows == 0) { *done = false; return 0; } // (the caller has nothing to launch)
+  if (ctx->query_in_flight) { // the block is the context's: the walk of the previous call must have read it
+    SJ_TRY(ctx, hipEventSynchronize(ctx->ev_query));
+    ctx->query_in_flight = false;
+  }
+  if (!ctx->ev_query) { SJ_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_query, hipEventDisableTiming)); }
+  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, 256 + size_t(rows) * sizeof(uint32_t));
+  if (rc) { return rc; }
+  if (workspace) {
+    rc = ensure_tmp(ctx, workspace);
+    if (rc) { return rc; }
+  }
+  SJ_TRY(ctx, hipMemsetAsync(ctx->d_query, 0, 256, s));
+  launch_query_check_table(static_cast<const doc_span_dev *>(docs_dev), docs, tape_words, string_bytes, reinterpret_cast<uint32_t *>(ctx->d_query), s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint32_t *const bad = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192); // (the pinned block's last slot, as in sjgpu_at_pointers_device)
+  SJ_TRY(ctx, hipMemcpyAsync(bad, ctx->d_query, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  if (*bad) { return SJGPU_E_BADARG; }
+  *done = false;
+  return 0;
+}
+} // namespace
+
+extern "C" {
+
+int sjgpu_object_fields_from_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                                          uint32_t docs, const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev,
+                                          void *key_value_dev, void *key_tag_dev, void *value_dev, void *tag_dev, uint64_t field_cap, void *stream, uint64_t *fields_out) {
+  if (fields_out) { *fields_out = 0; }
+  if (!string_buf_dev || !offsets_dev || !fields_out || (rows && !status_dev) || (field_cap && (!key_value_dev || !key_tag_dev || !value_dev || !tag_dev))) { return SJGPU_E_BADARG; }
+  if ((reinterpret_cast<uintptr_t>(offsets_dev) & 3u) || (reinterpret_cast<uintptr_t>(key_value_dev) & 7u) || (reinterpret_cast<uintptr_t>(value_dev) & 7u)) { return SJGPU_E_BADARG; }
+  hipStream_t s = nullptr;
+  bool done = true;
+  const int rc = fields_begin(ctx, tape_dev, tape_words, string_bytes, docs_dev, docs, root_value_dev, root_tag_dev, rows, rows ? paths_workspace_bytes(1, rows) : 0, stream, &s,
+                              &done);
+  if (done) { return rc; }
+  if (rows == 0) {
+    SJ_TRY(ctx, hipMemsetAsync(offsets_dev, 0, sizeof(uint32_t), s));
+    SJ_TRY(ctx, hipStreamSynchronize(s));
+    return 0;
+  }
+  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
+  const uint64_t *tape = static_cast<const uint64_t *>(tape_dev);
+  const uint64_t *root_value = static_cast<const uint64_t *>(root_value_dev);
+  uint32_t *where = reinterpret_cast<uint32_t *>(ctx->d_query + 256);
+  const void *total_dev = launch_object_fields_count(tape, table, docs, root_value, static_cast<const uint8_t *>(root_tag_dev), rows, where, offsets,
+                                                     static_cast<uint8_t *>(status_dev), ctx->d_tmp, s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
+  SJ_TRY(ctx, hipMemcpyAsync(total, total_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  const uint64_t fields = *total;
+  *fields_out = fields;
+  if (fields > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
+  if (fields > field_cap) { return SJGPU_E_OVERFLOW; }
+  if (fields) {
+    launch_object_fields_fill(tape, static_cast<const uint8_t *>(string_buf_dev), table, root_value, rows, where, offsets, static_cast<uint64_t *>(key_value_dev),
+                              static_cast<uint8_t *>(key_tag_dev), static_cast<uint64_t *>(value_dev), static_cast<uint8_t *>(tag_dev), s);
+    SJ_TRY(ctx, hipGetLastError());
+    SJ_TRY(ctx, hipStreamSynchronize(s)); // (the verdicts and the workspace are free again when the call returns)
+  }
+  return 0;
+}
+
+// only enqueued behind the table check: the event that guards the context's block guards the verdicts
+int sjgpu_cell_sizes_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *docs_dev, uint32_t docs, const void *root_value_dev, const void *root_tag_dev,
+                            uint32_t rows, void *size_dev, void *code_dev, void *stream) {
+  if ((rows && (!size_dev || !code_dev)) || (reinterpret_cast<uintptr_t>(size_dev) & 3u)) { return SJGPU_E_BADARG; }
+  hipStream_t s = nullptr;
+  bool done = true;
+  // (no string is read: the table's string_begin words, 32 bits each, have no end to stay below)
+  const int rc = fields_begin(ctx, tape_dev, tape_words, 0xFFFFFFFFull, docs_dev, docs, root_value_dev, root_tag_dev, rows, 0, stream, &s, &done);
+  if (done || rows == 0) { return rc; }
+  launch_cell_sizes(static_cast<const uint64_t *>(tape_dev), static_cast<const doc_span_dev *>(docs_dev), docs, static_cast<const uint64_t *>(root_value_dev),
+                    static_cast<const uint8_t *>(root_tag_dev), rows, reinterpret_cast<uint32_t *>(ctx->d_query + 256), static_cast<uint32_t *>(size_dev),
+                    static_cast<uint8_t *>(code_dev), s);
+  SJ_TRY(ctx, hipGetLastError());
+  SJ_TRY(ctx, hipEventRecord(ctx->ev_query, s));
+  ctx->query_in_flight = true;
   return 0;
 }
 

@@ -318,6 +318,19 @@ const void *launch_paths_rooted_count(const uint64_t *tape, const uint8_t *strin
 void launch_paths_rooted_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, const uint64_t *root_value, uint32_t rows, const uint32_t *where,
                               const uint8_t *program, uint32_t levels_at, uint32_t tokens_at, uint32_t keys_at, uint32_t K, const uint32_t *offsets, uint64_t *value, uint8_t *tag,
                               hipStream_t s);
+// ---- the fields of the cells' objects, the sizes of the cells' containers (sjgpu_query.hip: sjgpu_object_fields_from_cells_device, sjgpu_cell_sizes_device,
+// include/sjgpu_fields.h) ----------------------------------------------------------------------------------------------------------------------------------------
+// rows >= 1, docs >= 0, rows + 1 entries the scan takes; a table that passed the check; where[0 .. rows) (device memory): k_rows_locate's verdicts, made here.
+// launch_object_fields_count: status[r] and, in offsets[0 .. rows], the exclusive sum of the roots' field counts (an opening word's count field; walked only where it
+// reads saturated) -> the device address of the 64-bit total (workspace: paths_workspace_bytes(1, rows), 256-byte aligned).  launch_object_fields_fill, when the total
+// fits: field j of root r to the four rows at offsets[r] + j, never at or beyond offsets[r + 1]; what the walk did not reach below it is padded (tags 20, words 0).
+const void *launch_object_fields_count(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows,
+                                       uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s);
+void launch_object_fields_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, const uint64_t *root_value, uint32_t rows, const uint32_t *where,
+                               const uint32_t *offsets, uint64_t *key_value, uint8_t *key_tag, uint64_t *value, uint8_t *tag, hipStream_t s);
+// size[r] / code[r]: the count field of a located container's opening word and 0, or 0 and the root's code (a scalar: INCORRECT_TYPE)
+void launch_cell_sizes(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows, uint32_t *where,
+                       uint32_t *size, uint8_t *code, hipStream_t s);
 // ---- the same cells, breadth first (sjgpu_query.hip: sjgpu_at_paths_wide_device) ------------------------------------------------------------------------
 // The whole call behind the table check, K >= 1 and docs >= 1: the annotation of the tape (a head bit and a nesting depth per word), the starting frontier, the
 // levels of every path with their 4-byte read-backs of frontier sizes (into *readback: host memory, pinned where the copy is a real one), statuses, offsets and

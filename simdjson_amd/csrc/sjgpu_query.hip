@@ -1,7 +1,8 @@
 // simdjson_amd/csrc/sjgpu_query.hip -- queries over device tapes: a batched dom::element::at_pointer (sjgpu_at_pointers_device) and the
 // string column as offsets + characters (sjgpu_gather_strings_device).  Contract: include/sjgpu_query.h.  The same walk rooted at the cells of a
 // column (sjgpu_at_pointers_from_cells_device, include/sjgpu_rows.h) is at the end of the kernels, and behind it the paths rooted the same way
-// (sjgpu_at_paths_from_cells_device, include/sjgpu_lists.h).
+// (sjgpu_at_paths_from_cells_device, include/sjgpu_lists.h), and the fields and sizes of the cells' containers (sjgpu_object_fields_from_cells_device,
+// sjgpu_cell_sizes_device, include/sjgpu_fields.h).
 //
 // The walk.  K pointers x docs documents = K * docs CELLS; one lane walks one cell, the lanes of a workgroup take consecutive documents of ONE
 // pointer: the column stores are coalesced, the workgroup's pointer -- its tokens as sj_query_program.h compiled them and its
@@ -113,16 +114,19 @@ __device__ __forceinline__ u32 walk_tokens(const u64 *__restrict__ tape, const u
   return 0;
 }
 
+// the value word of a string cell whose tape word is w -- a string element, or an object's key (k_object_fields): (length << 32) | the absolute offset of its first byte
+__device__ __forceinline__ u64 string_cell_value(const u8 *__restrict__ sbuf, u64 w, u64 str_base, u64 str_end) {
+  const u64 rec = str_base + (w & PAYLOAD);
+  const u32 len = rec + 4u <= str_end ? *reinterpret_cast<const u32_unaligned *>(sbuf + rec) : 0u;
+  return (u64(len) << 32) | ((rec + 4u) & LOW32);
+}
+
 // the value word of a cell that holds the element at word `cur` (include/sjgpu_query.h); its tag is w >> 56
 __device__ __forceinline__ u64 cell_value(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 cur, u64 w, u64 base, u64 doc_end, u64 str_base, u64 str_end) {
   const u32 kind = u32(w >> 56);
   if (is_number_tag(kind)) { return cur + 1u < doc_end ? tape[cur + 1u] : 0; }
   if (kind == 't') { return 1; }
-  if (kind == '"') {
-    const u64 rec = str_base + (w & PAYLOAD);
-    const u32 len = rec + 4u <= str_end ? *reinterpret_cast<const u32_unaligned *>(sbuf + rec) : 0u;
-    return (u64(len) << 32) | ((rec + 4u) & LOW32);
-  }
+  if (kind == '"') { return string_cell_value(sbuf, w, str_base, str_end); }
   if (is_container_tag(kind)) { return ((base + (w & LOW32)) << 32) | cur; }
   return 0;
 }
@@ -762,6 +766,8 @@ constexpr u32 ROWS_SPECIAL = 0xFFFFFFF0u;
 __device__ __forceinline__ bool is_query_code(u32 t) {
   return t == QUERY_INCORRECT_TYPE || t == QUERY_INDEX_OUT_OF_BOUNDS || t == QUERY_NO_SUCH_FIELD || t == QUERY_INVALID_JSON_POINTER;
 }
+// the code of a verdict above ROWS_SPECIAL
+__device__ __forceinline__ u32 rows_code(u32 m) { return (m & 15u) + 16u; }
 
 // one lane per root.  A container cell is followed only when its opening index c lies INSIDE a document (behind its root word), the word there carries the
 // cell's tag and points where the cell's high half says: log2(docs) table reads, one tape word.
@@ -806,7 +812,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_pointers_rooted(const u64 
   u32 out_tag;
   u64 out_value = 0;
   if (m > ROWS_SPECIAL) {
-    out_tag = (m & 15u) + 16u;
+    out_tag = rows_code(m);
   } else if (m == ROWS_SPECIAL) {
     if (qp.code) {
       out_tag = qp.code;
@@ -869,7 +875,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_paths_rooted(const u64 *__
   if (go) {
     const u32 m = where[r64];
     if (m > ROWS_SPECIAL) {
-      code = (m & 15u) + 16u;
+      code = rows_code(m);
     } else if (m < ROWS_SPECIAL) { // (ROWS_SPECIAL itself: a scalar, status 0 and nothing)
       const uint4 a = *reinterpret_cast<const uint4 *>(table + m), b = *reinterpret_cast<const uint4 *>(table + m + 1u);
       const u64 base = a.z, doc_end = b.z;
@@ -883,6 +889,118 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_at_paths_rooted(const u64 *__
   }
   if (FILL) { return; }
   paths_count_done(active, cell, count, code, rows, row_blocks, offsets, status, block_sums, s_sum);
+}
+
+// ---- the fields (include/sjgpu_fields.h: sjgpu_object_fields_from_cells_device, sjgpu_cell_sizes_device) --------------------------------------------------
+// `for (dom::key_value_pair f : dom::object(e))` of every root cell of one row: the fields of each cell's object as one ragged pair of rows, keys as string cells and
+// values as cells, counted / scanned / filled like the lists -- one lane per root, consecutive lanes consecutive roots, k_rows_locate's verdicts.  No path, no
+// program, no key area.  The count does NOT walk: an opening word carries its scope's count in bits 32 .. 55 (the reference's tape_ref::scope_count), saturated at
+// 0xFFFFFF; only a count that reads saturated is walked.  The fill walks once and never trusts the count: it stops at the cell's last slot and pads what it did not reach.
+constexpr u32 SCOPE_COUNT_SATURATED = 0xFFFFFFu;
+__device__ __forceinline__ u32 scope_count(u64 w) { return u32(w >> 32) & SCOPE_COUNT_SATURATED; }
+
+// the fields of the object that opens at word `cur` (its word: w), in the tape's order; outer: the end of what surrounds it (the cell's high half cut to the
+// document's end).  FILL: field j to the four rows at out + j while out + j < out_end, and the slots behind the last field, up to out_end, padded with
+// NO_SUCH_FIELD and zeros; else the fields are counted.  -> the count
+template <bool FILL>
+__device__ __forceinline__ u32 walk_fields(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 cur, u64 w, u64 outer, u64 base, u64 doc_end, u64 str_base, u64 str_end,
+                                           u64 out, u64 out_end, u64 *__restrict__ key_value, u8 *__restrict__ key_tag, u64 *__restrict__ value, u8 *__restrict__ tag) {
+  u64 end = base + (w & LOW32);
+  end = end > cur ? end - 1u : cur; // the closing word
+  end = end < outer ? end : outer;
+  u64 i = cur + 1u; // the first key
+  u32 count = 0;
+  while (i + 1u < end && (!FILL || out < out_end)) { // a key word and the first word of its value
+    const u64 vw = tape[i + 1u];
+    if (FILL) {
+      key_tag[out] = u8('"');
+      key_value[out] = string_cell_value(sbuf, tape[i], str_base, str_end);
+      tag[out] = u8(vw >> 56);
+      value[out] = cell_value(tape, sbuf, i + 1u, vw, base, doc_end, str_base, str_end);
+      out++;
+    }
+    count++;
+    i = behind(i + 1u, vw, base, end);
+  }
+  if (FILL) {
+    for (; out < out_end; out++) { // (a count field that claims more than the walk finds)
+      key_tag[out] = u8(QUERY_NO_SUCH_FIELD);
+      key_value[out] = 0;
+      tag[out] = u8(QUERY_NO_SUCH_FIELD);
+      value[out] = 0;
+    }
+  }
+  return count;
+}
+
+// grid: ceil(rows / 256) workgroups; lane = root.  status: 0 for a located object, INCORRECT_TYPE for a located array and for a scalar, else the verdict's code
+__global__ __launch_bounds__(QUERY_THREADS) void k_object_fields_count(const u64 *__restrict__ tape, const doc_span_dev *__restrict__ table, const u64 *__restrict__ root_value,
+                                                                     const u32 *__restrict__ where, u32 rows, u32 *__restrict__ offsets, u8 *__restrict__ status,
+                                                                     u64 *__restrict__ block_sums) {
+  __shared__ u64 s_sum[QUERY_THREADS / 64];
+  const u64 r64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  const bool active = r64 < rows;
+  u32 count = 0, code = 0;
+  if (active) {
+    const u32 m = where[r64];
+    if (m > ROWS_SPECIAL) {
+      code = rows_code(m);
+    } else if (m == ROWS_SPECIAL) {
+      code = QUERY_INCORRECT_TYPE;
+    } else {
+      const u64 v = root_value[r64];
+      const u64 cur = v & LOW32, w = tape[cur]; // (k_rows_locate found cur inside the document, and w to agree with the cell)
+      if (u32(w >> 56) != '{') {
+        code = QUERY_INCORRECT_TYPE;
+      } else {
+        count = scope_count(w);
+        if (count == SCOPE_COUNT_SATURATED) { // 16 777 215 fields or more: the one case that is walked
+          const u64 base = table[m].tape_begin, doc_end = table[m + 1u].tape_begin;
+          const u64 outer = (v >> 32) < doc_end ? (v >> 32) : doc_end;
+          count = walk_fields<false>(tape, nullptr, cur, w, outer, base, doc_end, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr);
+        }
+      }
+    }
+  }
+  paths_count_done(active, r64, count, code, rows, gridDim.x, offsets, status, block_sums, s_sum);
+}
+
+// grid: ceil(rows / 256) workgroups; lane = root.  The slots of root r are offsets[r] .. offsets[r + 1]: only a located object has any
+__global__ __launch_bounds__(QUERY_THREADS) void k_object_fields_fill(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, const doc_span_dev *__restrict__ table,
+                                                                    const u64 *__restrict__ root_value, const u32 *__restrict__ where, u32 rows,
+                                                                    const u32 *__restrict__ offsets, u64 *__restrict__ key_value, u8 *__restrict__ key_tag,
+                                                                    u64 *__restrict__ value, u8 *__restrict__ tag) {
+  const u64 r64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (r64 >= rows) { return; }
+  const u64 out = offsets[r64], out_end = offsets[r64 + 1u];
+  if (out >= out_end) { return; }
+  const u32 m = where[r64];
+  if (m >= ROWS_SPECIAL) { return; } // (the count gave such a root no slot)
+  const uint4 a = *reinterpret_cast<const uint4 *>(table + m), b = *reinterpret_cast<const uint4 *>(table + m + 1u);
+  const u64 base = a.z, doc_end = b.z;
+  const u64 str_base = a.w, str_end = b.w;
+  const u64 v = root_value[r64];
+  const u64 cur = v & LOW32, w = tape[cur];
+  const u64 outer = (v >> 32) < doc_end ? (v >> 32) : doc_end;
+  walk_fields<true>(tape, sbuf, cur, w, outer, base, doc_end, str_base, str_end, out, out_end, key_value, key_tag, value, tag);
+}
+
+// dom::object::size() / dom::array::size() of every root: the count field of a located container's opening word as it stands, no walk.  lane = root
+__global__ __launch_bounds__(QUERY_THREADS) void k_cell_sizes(const u64 *__restrict__ tape, const u64 *__restrict__ root_value, const u32 *__restrict__ where, u32 rows,
+                                                            u32 *__restrict__ size, u8 *__restrict__ code_out) {
+  const u64 r64 = u64(blockIdx.x) * QUERY_THREADS + threadIdx.x;
+  if (r64 >= rows) { return; }
+  const u32 m = where[r64];
+  u32 n = 0, code = 0;
+  if (m > ROWS_SPECIAL) {
+    code = rows_code(m);
+  } else if (m == ROWS_SPECIAL) {
+    code = QUERY_INCORRECT_TYPE;
+  } else {
+    n = scope_count(tape[root_value[r64] & LOW32]);
+  }
+  size[r64] = n;
+  code_out[r64] = u8(code);
 }
 
 static inline u32 blocks_of(u64 n, u32 per) { return u32((n + per - 1) / per); }
@@ -977,6 +1095,34 @@ void launch_paths_rooted_fill(const uint64_t *tape, const uint8_t *string_buf, c
   const u32 row_blocks = blocks_of(rows, QUERY_THREADS);
   hipLaunchKernelGGL(k_at_paths_rooted<true>, dim3(row_blocks * K), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, root_value, where, rows, program, levels_at, tokens_at,
                      keys_at, row_blocks, const_cast<u32 *>(offsets), static_cast<u8 *>(nullptr), static_cast<u64 *>(nullptr), value, tag);
+}
+
+// the fields of the roots' objects (include/sjgpu_fields.h): locate, count, the total, the scan -- the workspace and the control block of one rooted path
+const void *launch_object_fields_count(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows,
+                                       uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s) {
+  uint8_t *ws = static_cast<uint8_t *>(workspace);
+  gather_ctrl *ctrl = reinterpret_cast<gather_ctrl *>(ws);
+  u64 *block_sums = reinterpret_cast<u64 *>(ws + 256);
+  int *partial = reinterpret_cast<int *>(ws + 256 + paths_sums_bytes(1, rows));
+  const u32 row_blocks = blocks_of(rows, QUERY_THREADS);
+  hipLaunchKernelGGL(k_rows_locate, dim3(row_blocks), dim3(QUERY_THREADS), 0, s, tape, table, docs, root_value, root_tag, rows, where);
+  hipLaunchKernelGGL(k_object_fields_count, dim3(row_blocks), dim3(QUERY_THREADS), 0, s, tape, table, root_value, static_cast<const u32 *>(where), rows, offsets, status, block_sums);
+  hipLaunchKernelGGL(k_gather_total, dim3(1), dim3(QUERY_THREADS), 0, s, block_sums, row_blocks, rows, ctrl);
+  enqueue_scan(reinterpret_cast<int *>(offsets), rows + 1u, &ctrl->n_plus_1, partial, s);
+  return ctrl;
+}
+
+void launch_object_fields_fill(const uint64_t *tape, const uint8_t *string_buf, const doc_span_dev *table, const uint64_t *root_value, uint32_t rows, const uint32_t *where,
+                               const uint32_t *offsets, uint64_t *key_value, uint8_t *key_tag, uint64_t *value, uint8_t *tag, hipStream_t s) {
+  hipLaunchKernelGGL(k_object_fields_fill, dim3(blocks_of(rows, QUERY_THREADS)), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, root_value, where, rows, offsets, key_value,
+                     key_tag, value, tag);
+}
+
+void launch_cell_sizes(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows, uint32_t *where,
+                       uint32_t *size, uint8_t *code, hipStream_t s) {
+  const u32 row_blocks = blocks_of(rows, QUERY_THREADS);
+  hipLaunchKernelGGL(k_rows_locate, dim3(row_blocks), dim3(QUERY_THREADS), 0, s, tape, table, docs, root_value, root_tag, rows, where);
+  hipLaunchKernelGGL(k_cell_sizes, dim3(row_blocks), dim3(QUERY_THREADS), 0, s, tape, root_value, static_cast<const u32 *>(where), rows, size, code);
 }
 
 // ---- the wide call's level loop ---------------------------------------------------------------------------------------------------------------------
