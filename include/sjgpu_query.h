@@ -49,7 +49,10 @@ extern "C" {
  * Synchronisation: the table check reads one word back, so the call waits for what `stream` held when it was called and for that
  * check; the walk itself is only enqueued -- the columns are complete when `stream` has reached the end of the call's work.  The
  * compiled pointers go up through a block the context owns: a call waits for the walk of the context's previous call before it
- * writes that block again. */
+ * writes that block again.
+ * Destroying a context: sjgpu_ctx_destroy (sjgpu.h) waits for the context's OWN stream only, never for a stream the caller passed to
+ * a *_device call, and then parks the context, workspaces included, for the next sjgpu_ctx_create.  The caller must therefore have
+ * waited for every stream that still holds work of the context -- an enqueued walk of this call, say -- before it destroys it. */
 int sjgpu_at_pointers_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes,
                              const void *docs_dev, uint32_t docs, const uint8_t *pointers, const uint32_t *pointer_lens, uint32_t K,
                              void *value_dev, void *tag_dev, void *stream);
