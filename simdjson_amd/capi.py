@@ -80,6 +80,12 @@ SJGPU_E_OVERFLOW = -5  # (include/sjgpu.h) an output was too small; the calls wi
 FIELDS_EXPORTS = ["sjgpu_object_fields_from_cells_device", "sjgpu_cell_sizes_device"]
 
 
+# what include/sjgpu_dict.h declares (dictionaries over device cells: a row of string cells as codes + a dictionary in order of first occurrence, and the census of a
+# value row per code); the bindings are the free functions of simdjson_amd/dictionary.py
+DICT_EXPORTS = ["sjgpu_dictionary_encode_device", "sjgpu_cell_kinds_by_code_device"]
+SJGPU_E_INTERNAL = -7  # (include/sjgpu_dict.h) a bounded loop of the library ran out: a bug of the library
+
+
 def infer_getters(kinds):
     """The getter a loader would ask of each row, from its census (kinds: K x 16 counts as sjgpu_cell_kinds_device leaves them) -> list of K SJGPU_GET_* or 0.
     The ELEMENTS of a row are its cells except the nulls and the codes 17 / 19 / 20 / 22 (they become invalid bits under any getter):
@@ -218,6 +224,10 @@ def load_library():
                                                         ctypes.c_uint64, vp, u64p]
     L.sjgpu_cell_sizes_device.restype = ctypes.c_int
     L.sjgpu_cell_sizes_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp]
+    L.sjgpu_dictionary_encode_device.restype = ctypes.c_int
+    L.sjgpu_dictionary_encode_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, ctypes.c_uint64, vp, u64p]
+    L.sjgpu_cell_kinds_by_code_device.restype = ctypes.c_int
+    L.sjgpu_cell_kinds_by_code_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int

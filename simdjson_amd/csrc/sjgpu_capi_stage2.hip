@@ -8,6 +8,7 @@
 #include "sjgpu_lists.h"
 #include "sjgpu_cast.h"
 #include "sjgpu_fields.h"
+#include "sjgpu_dict.h"
 #include "sj_path_program.h"
 
 extern "C" {
@@ -744,6 +745,55 @@ int sjgpu_cast_cells_device(sjgpu_ctx *ctx, const void *value_dev, const void *t
   SJ_TRY(ctx, hipSetDevice(ctx->device));
   SJ_TRY(ctx, launch_cast_cells(static_cast<const uint64_t *>(value_dev), static_cast<const uint8_t *>(tag_dev), n, K, getters, static_cast<uint64_t *>(value_out_dev),
                                 static_cast<uint8_t *>(code_out_dev), static_cast<uint64_t *>(valid_out_dev), static_cast<uint32_t *>(counts_out_dev), pick(ctx, stream)));
+  SJ_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+// ---- a dictionary of a row of string cells, the census per code (sjgpu_dict.hip; include/sjgpu_dict.h) -----------------------------------------------------
+// The encode reads the cells and the string buffer alone: no block of the context and no event, its table lies in d_tmp.  The codes are enqueued in front of the
+// read-back: they are complete whatever the capacity says
+int sjgpu_dictionary_encode_device(sjgpu_ctx *ctx, const void *string_buf_dev, uint64_t string_bytes, const void *value_row_dev, const void *tag_row_dev, uint32_t n,
+                                   void *codes_dev, void *dict_value_dev, void *dict_tag_dev, void *dict_first_dev, void *dict_count_dev, uint64_t dict_cap, void *stream,
+                                   uint64_t *distinct_out) {
+  if (distinct_out) { *distinct_out = 0; }
+  if (!ctx || !distinct_out ||
+      !dict_encode_args_ok(string_buf_dev, string_bytes, value_row_dev, tag_row_dev, n, codes_dev, dict_value_dev, dict_tag_dev, dict_first_dev, dict_count_dev, dict_cap)) {
+    return SJGPU_E_BADARG;
+  }
+  if (n == 0) { return 0; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_tmp(ctx, dict_workspace_bytes(n));
+  if (rc) { return rc; }
+  hipStream_t s = pick(ctx, stream);
+  const uint64_t *value = static_cast<const uint64_t *>(value_row_dev);
+  const dict_result_dev *result_dev = nullptr;
+  SJ_TRY(ctx, launch_dict_encode(value, static_cast<const uint8_t *>(tag_row_dev), n, static_cast<const uint8_t *>(string_buf_dev), string_bytes,
+                                 static_cast<int32_t *>(codes_dev), ctx->d_tmp, s, &result_dev));
+  SJ_TRY(ctx, hipGetLastError());
+  dict_result_dev *const result = reinterpret_cast<dict_result_dev *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192); // (the pinned block's last slot, as in the gather)
+  SJ_TRY(ctx, hipMemcpyAsync(result, result_dev, sizeof(dict_result_dev), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  if (result->failed) { return SJGPU_E_INTERNAL; }
+  const uint64_t distinct = result->distinct;
+  *distinct_out = distinct;
+  if (distinct > dict_cap) { return SJGPU_E_OVERFLOW; }
+  if (distinct) {
+    launch_dict_fill(value, n, ctx->d_tmp, static_cast<uint64_t *>(dict_value_dev), static_cast<uint8_t *>(dict_tag_dev), static_cast<uint32_t *>(dict_first_dev),
+                     static_cast<uint32_t *>(dict_count_dev), s);
+    SJ_TRY(ctx, hipGetLastError());
+    SJ_TRY(ctx, hipStreamSynchronize(s)); // (the workspace is free again when the call returns)
+  }
+  return 0;
+}
+
+// elementwise over the cells and their codes, as sjgpu_cell_kinds_device: a memset of the counters and one launch, only enqueued
+int sjgpu_cell_kinds_by_code_device(sjgpu_ctx *ctx, const void *codes_dev, const void *value_dev, const void *tag_dev, uint32_t n, uint32_t groups, void *kinds_dev,
+                                    void *stream) {
+  if (!ctx || !cell_kinds_by_code_args_ok(codes_dev, value_dev, tag_dev, n, groups, kinds_dev)) { return SJGPU_E_BADARG; }
+  if (groups == 0) { return 0; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  SJ_TRY(ctx, launch_cell_kinds_by_code(static_cast<const int32_t *>(codes_dev), static_cast<const uint64_t *>(value_dev), static_cast<const uint8_t *>(tag_dev), n, groups,
+                                        static_cast<uint32_t *>(kinds_dev), pick(ctx, stream)));
   SJ_TRY(ctx, hipGetLastError());
   return 0;
 }

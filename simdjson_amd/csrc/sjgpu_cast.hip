@@ -13,6 +13,7 @@
 // compiler's double(int64_t) and double(uint64_t), round to nearest even.
 #include "sjgpu_device.h"
 #include "sjgpu_cast.h"
+#include "sj_cell_kinds.h"
 
 namespace sjgpu {
 namespace {
@@ -121,28 +122,7 @@ __global__ __launch_bounds__(CAST_THREADS) void k_cast_cells(const u64 *value, c
   }
 }
 
-constexpr u32 KIND_SLOTS = 16, KIND_NEGATIVE = 9, KIND_OTHER = 14, KIND_NONE = 15;
-
-// the census slot of a tag byte (include/sjgpu_cast.h); slot 9 is not a tag's
-__device__ __forceinline__ u32 kind_slot(u32 t) {
-  switch (t) {
-    case '{': return 0;
-    case '[': return 1;
-    case '"': return 2;
-    case 'l': return 3;
-    case 'u': return 4;
-    case 'd': return 5;
-    case 't': return 6;
-    case 'f': return 7;
-    case 'n': return 8;
-    case 17: return 10;
-    case 19: return 11;
-    case 20: return 12;
-    case 22: return 13;
-    default: return KIND_OTHER;
-  }
-}
-
+// (the census slots and kind_slot: sj_cell_kinds.h, shared with the census by code of sjgpu_dict.hip)
 __global__ __launch_bounds__(CAST_THREADS) void k_cell_kinds(const u64 *__restrict__ value, const u8 *__restrict__ tag, u32 n, u32 row_blocks, u32 *__restrict__ kinds) {
   __shared__ u32 s_part[CAST_WAVES][KIND_SLOTS];
   __shared__ u8 s_slot[256]; // kind_slot of every byte, made once per workgroup (256 lanes, 256 bytes): a table read per cell instead of a divergent switch

@@ -366,6 +366,35 @@ inline bool cast_cells_args_ok(const void *value, const void *tag, uint32_t n, u
 hipError_t launch_cell_kinds(const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t K, uint32_t *kinds, hipStream_t s);
 hipError_t launch_cast_cells(const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t K, const uint8_t *getters, uint64_t *value_out, uint8_t *code_out,
                              uint64_t *valid_out, uint32_t *counts, hipStream_t s);
+// ---- a dictionary of a row of string cells, the census per code (sjgpu_dict.hip: sjgpu_dictionary_encode_device, sjgpu_cell_kinds_by_code_device,
+// include/sjgpu_dict.h) -----------------------------------------------------------------------------------------------------------------------------------------
+// What the two calls refuse before anything is read or enqueued (the C-ABI adds the null context and *distinct_out); the CPU tier asks the same functions.
+constexpr uint32_t DICT_MAX_ROWS = 1u << 30; // the table has 2 n slots at the least, and a slot's index is a u32 whose top value means "none"
+inline bool dict_encode_args_ok(const void *string_buf, uint64_t string_bytes, const void *value_row, const void *tag_row, uint32_t n, const void *codes, const void *dict_value,
+                                const void *dict_tag, const void *dict_first, const void *dict_count, uint64_t dict_cap) {
+  if (n > DICT_MAX_ROWS || string_bytes > 0xFFFFFFFFull) { return false; }
+  if (cast_misaligned(value_row, 8) || cast_misaligned(dict_value, 8) || cast_misaligned(codes, 4) || cast_misaligned(dict_first, 4) || cast_misaligned(dict_count, 4)) { return false; }
+  if (!string_buf || (n && (!value_row || !tag_row || !codes))) { return false; }
+  return !dict_cap || (dict_value && dict_tag && dict_first && dict_count);
+}
+inline bool cell_kinds_by_code_args_ok(const void *codes, const void *value, const void *tag, uint32_t n, uint32_t groups, const void *kinds) {
+  if (cast_misaligned(codes, 4) || cast_misaligned(value, 8) || cast_misaligned(kinds, 4) || uint64_t(groups) * 16 > 0xFFFFFFFFull) { return false; }
+  if (groups && !kinds) { return false; }
+  return !(groups && n) || (codes && value && tag);
+}
+// what the encode leaves for the host, 8 bytes at a 4-byte aligned address of the workspace: the distinct strings, and non-zero when a probe ran out of slots
+struct dict_result_dev {
+  uint32_t distinct, failed;
+};
+// Arguments that passed the check, 1 <= n <= DICT_MAX_ROWS; workspace: dict_workspace_bytes(n), 256-byte aligned.  Three memsets, the insert, the heads, the scan
+// and the codes: codes[0 .. n) are complete when they have run, *result is where the dict_result_dev lies.  -> what the memsets returned
+size_t dict_workspace_bytes(uint32_t n);
+hipError_t launch_dict_encode(const uint64_t *value, const uint8_t *tag, uint32_t n, const uint8_t *string_buf, uint64_t string_bytes, int32_t *codes, void *workspace,
+                              hipStream_t s, const dict_result_dev **result);
+// behind it, over the same workspace, when the distinct strings fit: entry j of the four arrays for every j < distinct
+void launch_dict_fill(const uint64_t *value, uint32_t n, void *workspace, uint64_t *dict_value, uint8_t *dict_tag, uint32_t *dict_first, uint32_t *dict_count, hipStream_t s);
+// a memset of the groups * 16 counters and, when n > 0, one launch: up to 512 groups the histogram lies in LDS, above that every cell adds to global memory
+hipError_t launch_cell_kinds_by_code(const int32_t *codes, const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t groups, uint32_t *kinds, hipStream_t s);
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);
