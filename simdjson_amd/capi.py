@@ -86,6 +86,11 @@ DICT_EXPORTS = ["sjgpu_dictionary_encode_device", "sjgpu_cell_kinds_by_code_devi
 SJGPU_E_INTERNAL = -7  # (include/sjgpu_dict.h) a bounded loop of the library ran out: a bug of the library
 
 
+# what include/sjgpu_json.h declares (cells as JSON text: minify(element) per cell into offsets + chars); the bindings are the free functions of
+# simdjson_amd/json_text.py
+JSON_EXPORTS = ["sjgpu_serialize_cells_device"]
+
+
 def infer_getters(kinds):
     """The getter a loader would ask of each row, from its census (kinds: K x 16 counts as sjgpu_cell_kinds_device leaves them) -> list of K SJGPU_GET_* or 0.
     The ELEMENTS of a row are its cells except the nulls and the codes 17 / 19 / 20 / 22 (they become invalid bits under any getter):
@@ -228,6 +233,8 @@ def load_library():
     L.sjgpu_dictionary_encode_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_cell_kinds_by_code_device.restype = ctypes.c_int
     L.sjgpu_cell_kinds_by_code_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    L.sjgpu_serialize_cells_device.restype = ctypes.c_int
+    L.sjgpu_serialize_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int

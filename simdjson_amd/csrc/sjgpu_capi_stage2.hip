@@ -9,6 +9,7 @@
 #include "sjgpu_cast.h"
 #include "sjgpu_fields.h"
 #include "sjgpu_dict.h"
+#include "sjgpu_json.h"
 #include "sj_path_program.h"
 
 extern "C" {
@@ -724,6 +725,48 @@ int sjgpu_cell_sizes_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_
   SJ_TRY(ctx, hipGetLastError());
   SJ_TRY(ctx, hipEventRecord(ctx->ev_query, s));
   ctx->query_in_flight = true;
+  return 0;
+}
+
+// ---- cells as JSON text (k_json_count, k_json_fill in sjgpu_json.hip; include/sjgpu_json.h) --------------------------------------------------------------
+// The fields call's prologue and shape: the verdicts in the context's block, the count's total read back, the fill only when it fits
+int sjgpu_serialize_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                                 const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev, uint64_t chars_cap,
+                                 void *stream, uint64_t *bytes_out) {
+  if (bytes_out) { *bytes_out = 0; }
+  if (!string_buf_dev || !offsets_dev || !bytes_out || (rows && !status_dev) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
+  if (reinterpret_cast<uintptr_t>(offsets_dev) & 3u) { return SJGPU_E_BADARG; }
+  hipStream_t s = nullptr;
+  bool done = true;
+  const int rc = fields_begin(ctx, tape_dev, tape_words, string_bytes, docs_dev, docs, root_value_dev, root_tag_dev, rows, rows ? json_workspace_bytes(rows) : 0, stream, &s, &done);
+  if (done) { return rc; }
+  if (rows == 0) {
+    SJ_TRY(ctx, hipMemsetAsync(offsets_dev, 0, sizeof(uint32_t), s));
+    SJ_TRY(ctx, hipStreamSynchronize(s));
+    return 0;
+  }
+  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
+  const uint64_t *tape = static_cast<const uint64_t *>(tape_dev);
+  const uint8_t *sbuf = static_cast<const uint8_t *>(string_buf_dev);
+  const uint64_t *root_value = static_cast<const uint64_t *>(root_value_dev);
+  const uint8_t *root_tag = static_cast<const uint8_t *>(root_tag_dev);
+  uint32_t *where = reinterpret_cast<uint32_t *>(ctx->d_query + 256);
+  const count_total_dev *total_dev = launch_json_count(tape, sbuf, string_bytes, table, docs, root_value, root_tag, rows, where, offsets, static_cast<uint8_t *>(status_dev),
+                                                       ctx->d_tmp, s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
+  SJ_TRY(ctx, hipMemcpyAsync(total, &total_dev->total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  const uint64_t bytes = *total;
+  *bytes_out = bytes;
+  if (bytes > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
+  if (bytes > chars_cap) { return SJGPU_E_OVERFLOW; }
+  if (bytes) {
+    launch_json_fill(tape, sbuf, string_bytes, table, root_value, root_tag, rows, where, offsets, static_cast<uint8_t *>(chars_dev), ctx->d_tmp, s);
+    SJ_TRY(ctx, hipGetLastError());
+    SJ_TRY(ctx, hipStreamSynchronize(s)); // (the verdicts and the workspace are free again when the call returns)
+  }
   return 0;
 }
 

@@ -331,6 +331,22 @@ void launch_object_fields_fill(const uint64_t *tape, const uint8_t *string_buf, 
 // size[r] / code[r]: the count field of a located container's opening word and 0, or 0 and the root's code (a scalar: INCORRECT_TYPE)
 void launch_cell_sizes(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows, uint32_t *where,
                        uint32_t *size, uint8_t *code, hipStream_t s);
+// ---- what k_rows_locate leaves per root, for every unit that reads it (sjgpu_query.hip, sjgpu_json.hip) --------------------------------------------------------
+//   d < ROWS_SPECIAL             a container cell that agrees with the tape: the document it lies in
+//   ROWS_SPECIAL                 a scalar root
+//   ROWS_SPECIAL | (code - 16)   a root that answers `code`: rows_code
+constexpr uint32_t ROWS_SPECIAL = 0xFFFFFFF0u;
+constexpr uint32_t rows_code(uint32_t m) { return (m & 15u) + 16u; }
+// where[0 .. rows) (device memory) = the verdicts of the rows root cells; rows >= 1, docs >= 0, a table that passed the check
+void launch_rows_locate(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows, uint32_t *where,
+                        hipStream_t s);
+// what a count leaves in front of its scan, 16 bytes of device memory: the sum of the per-cell counts in 64 bits (the scan's words wrap at 2^32) and entries + 1, the
+// length of the scan.  launch_count_total: one workgroup adds the count kernel's `blocks` block sums
+struct count_total_dev {
+  uint64_t total;
+  uint32_t n_plus_1, pad;
+};
+void launch_count_total(const uint64_t *block_sums, uint32_t blocks, uint32_t entries, count_total_dev *ctrl, hipStream_t s);
 // ---- the same cells, breadth first (sjgpu_query.hip: sjgpu_at_paths_wide_device) ------------------------------------------------------------------------
 // The whole call behind the table check, K >= 1 and docs >= 1: the annotation of the tape (a head bit and a nesting depth per word), the starting frontier, the
 // levels of every path with their 4-byte read-backs of frontier sizes (into *readback: host memory, pinned where the copy is a real one), statuses, offsets and
@@ -395,6 +411,15 @@ hipError_t launch_dict_encode(const uint64_t *value, const uint8_t *tag, uint32_
 void launch_dict_fill(const uint64_t *value, uint32_t n, void *workspace, uint64_t *dict_value, uint8_t *dict_tag, uint32_t *dict_first, uint32_t *dict_count, hipStream_t s);
 // a memset of the groups * 16 counters and, when n > 0, one launch: up to 512 groups the histogram lies in LDS, above that every cell adds to global memory
 hipError_t launch_cell_kinds_by_code(const int32_t *codes, const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t groups, uint32_t *kinds, hipStream_t s);
+// ---- cells as JSON text (sjgpu_json.hip: sjgpu_serialize_cells_device, include/sjgpu_json.h) -----------------------------------------------------------------
+// rows >= 1, docs >= 0, rows + 1 entries the scan takes; a table that passed the check; where[0 .. rows) (device memory): k_rows_locate's verdicts, made here;
+// workspace: json_workspace_bytes(rows), 256-byte aligned, the same for both launches.  launch_json_count: status[r] and, in offsets[0 .. rows], the exclusive sum of the
+// cells' text lengths -> where the 64-bit total lies.  launch_json_fill, when the total fits: the bytes of cell r to chars[offsets[r] .. offsets[r + 1]), never beyond
+size_t json_workspace_bytes(uint32_t rows);
+const count_total_dev *launch_json_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value,
+                                         const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s);
+void launch_json_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                      uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s);
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);

@@ -1,0 +1,289 @@
+// simdjson_amd/csrc/sjgpu_json.hip -- the JSON text of every cell of one row (sjgpu_serialize_cells_device): simdjson::minify(element) for a batch of elements that
+// live on device tapes.  Contract: include/sjgpu_json.h.
+//
+//   k_rows_locate   (sjgpu_query.hip, shared) what every root is: a container that agrees with the tape and the document it lies in, a scalar, or a code
+//   k_json_count    one lane per cell, cells handed out grid-stride: the length of its text and its status.  A container is WALKED, word by word from its opening
+//                   word to its closing one, and everything the fill will rely on is decided here: every tag one of the ten, every string record inside its
+//                   document's part of the buffer, every number with its second word, every double finite, every closing word of the kind of the level it closes and
+//                   pointing back at an opening word that points just behind it, and the walk over exactly at the cell's high index.  Anything else: status 20, length 0.
+//   k_gather_total, enqueue_scan   (shared) the lengths' exclusive sum in place and their total in 64 bits
+//   k_json_fill     one lane per cell with bytes: the same walk, writing.  It never writes at or beyond offsets[r + 1], whatever the tape says by then.
+// The two passes are one template, walk_cell<FILL>.  The only fact of the format that is not local to a tape word is whether a string word is a KEY: it is when the
+// innermost open container is an object and its last word was not a key.  That is one bit per nesting level below the cell's root: levels 0 .. 63 are one 64-bit register,
+// deeper ones a strip of 63 words per resident lane in the workspace (4 096 levels in all; the parser stops at max_depth <= 4 095), touched only by a push or a pop
+// beyond level 63.  The grid is capped at JSON_MAX_WORKGROUPS so that the strips stay at 512 x 256 x 504 bytes = 63 MiB at the most; a call of fewer rows takes less.
+// No per-lane array is indexed at run time: digits and escapes go straight to their place in the output (sj_dtoa.h, sj_json_text.h).
+// Every loop is bounded by the cell's high - low words, by a string's length or by a number's 20 digits; no lane waits for another.
+// Cost, not hidden (include/sjgpu_json.h): one lane per cell, a double is converted in both passes, bytes leave one lane at a time.
+#include "sjgpu_device.h"
+#include "sjgpu_json.h"
+#include "sj_json_text.h"
+#include "sj_query_program.h"
+
+namespace sjgpu {
+namespace {
+
+constexpr u32 JSON_THREADS = 256;
+constexpr u32 JSON_MAX_WORKGROUPS = 512;
+constexpr u32 JSON_REGISTER_LEVELS = 64, JSON_STRIP_WORDS = 63, JSON_MAX_LEVELS = JSON_REGISTER_LEVELS + 64 * JSON_STRIP_WORDS;
+constexpr u64 LOW32 = 0xFFFFFFFFull, PAYLOAD = 0x00FFFFFFFFFFFFFFull;
+
+typedef u32 __attribute__((aligned(1))) u32_unaligned;
+
+// "is level L an object": a register for the first 64 levels, the lane's strip beyond
+struct level_bits {
+  u64 low;
+  u64 *strip;
+  __device__ __forceinline__ void set(u32 L, bool object) {
+    if (L < JSON_REGISTER_LEVELS) {
+      low = (low & ~(1ull << L)) | (u64(object) << L);
+    } else {
+      const u32 at = L - JSON_REGISTER_LEVELS;
+      const u64 bit = 1ull << (at & 63u);
+      const u64 word = strip[at >> 6]; // (what lies above the bit is of no level that is open: never read before it is set)
+      strip[at >> 6] = object ? word | bit : word & ~bit;
+    }
+  }
+  __device__ __forceinline__ bool get(u32 L) const {
+    if (L < JSON_REGISTER_LEVELS) { return (low >> L) & 1u; }
+    const u32 at = L - JSON_REGISTER_LEVELS;
+    return (strip[at >> 6] >> (at & 63u)) & 1u;
+  }
+};
+
+// where a lane writes: out[0 .. room), `at` counts on beyond it
+template <bool FILL>
+struct json_sink {
+  u8 *out;
+  u64 room, at;
+  __device__ __forceinline__ void put(u32 c) {
+    if (FILL && at < room) { out[at] = u8(c); }
+    at++;
+  }
+  __device__ __forceinline__ void put_literal(u32 t) { // t, f, n
+    if (t == 't') {
+      put('t'); put('r'); put('u'); put('e');
+    } else if (t == 'f') {
+      put('f'); put('a'); put('l'); put('s'); put('e');
+    } else {
+      put('n'); put('u'); put('l'); put('l');
+    }
+  }
+  // l, u or d with the value word v (a finite double)
+  __device__ __forceinline__ void put_number(u32 t, u64 v) {
+    u32 length = 0;
+    const bool fits = FILL && at + DTOA_MAX_BYTES <= room; // (24 >= the 20 of an integer)
+    if (!fits) { length = t == 'd' ? dtoa_length(v) : t == 'l' ? int64_text_length(v) : decimal_digits(v); }
+    if (FILL && (fits || at + length <= room)) {
+      u8 *p = out + at;
+      if (t == 'd') {
+        length = dtoa_write(v, p);
+      } else if (t == 'l') {
+        length = int64_text_write(v, p);
+      } else {
+        length = decimal_digits(v);
+        write_decimal(p, v, length);
+      }
+    }
+    at += length;
+  }
+  __device__ __forceinline__ void put_string(const u8 *s, u32 len) {
+    if (FILL) {
+      at += escape_write(s, len, out + (at < room ? at : room), at < room ? room - at : 0u);
+    } else {
+      at += escaped_length(s, len);
+    }
+  }
+};
+
+// The text of the container whose opening word is tape[low] and whose closing word is tape[high - 1] (k_rows_locate found both inside the document that begins at
+// `base`, and the opening word to say so).  -> true with the length in sink.at; false: the sub-tape is not well formed (only !FILL decides that in full -- the fill
+// runs behind a count that said true, keeps every bound and stops at the sink's room)
+template <bool FILL>
+__device__ __forceinline__ bool walk_cell(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 low, u64 high, u64 base, u64 str_base, u64 str_end, u64 *strip,
+                                          json_sink<FILL> &sink) {
+  level_bits levels = {0, strip};
+  u32 depth = 0, need = 0; // need: 0 nothing, 1 a comma, 2 a colon in front of the next word's text
+  bool in_object = false, key_next = false;
+  u64 i = low;
+  while (i < high) {
+    const u64 w = tape[i];
+    const u32 t = u32(w >> 56);
+    if (t == '}' || t == ']') {
+      if (depth == 0 || in_object != (t == '}') || (in_object && !key_next)) { return false; } // nothing open, the other kind, or a key without its value
+      if (!FILL) {
+        const u64 o = base + (w & LOW32);
+        if (o < low || o >= i) { return false; }
+        const u64 ow = tape[o];
+        if (u32(ow >> 56) != (in_object ? u32('{') : u32('[')) || base + (ow & LOW32) != i + 1u) { return false; }
+      }
+      sink.put(t);
+      depth--;
+      i++;
+      if (depth == 0) { return i == high; }
+      in_object = levels.get(depth - 1u);
+      key_next = in_object;
+      need = 1;
+      continue;
+    }
+    if (depth == 0 && i != low) { return false; }
+    const bool is_key = key_next;
+    if (is_key && t != '"') { return false; }
+    if (need == 1) { sink.put(','); }
+    if (need == 2) { sink.put(':'); }
+    if (t == '{' || t == '[') {
+      if (depth >= JSON_MAX_LEVELS) { return false; }
+      in_object = t == '{';
+      levels.set(depth, in_object);
+      depth++;
+      sink.put(t);
+      key_next = in_object;
+      need = 0;
+      i++;
+      continue;
+    }
+    if (depth == 0) { return false; } // (a cell's sub-tape begins with an opening word)
+    if (t == '"') {
+      const u64 rec = str_base + (w & PAYLOAD);
+      if (rec + 4u > str_end) { return false; }
+      const u32 len = *reinterpret_cast<const u32_unaligned *>(sbuf + rec);
+      if (rec + 4u + u64(len) > str_end) { return false; }
+      sink.put_string(sbuf + rec + 4u, len);
+      i++;
+    } else if (t == 'l' || t == 'u' || t == 'd') {
+      if (i + 1u >= high) { return false; }
+      const u64 v = tape[i + 1u];
+      if (t == 'd' && !dtoa_is_finite(v)) { return false; }
+      sink.put_number(t, v);
+      i += 2u;
+    } else if (t == 't' || t == 'f' || t == 'n') {
+      sink.put_literal(t);
+      i++;
+    } else {
+      return false;
+    }
+    need = is_key ? 2u : 1u;
+    key_next = in_object && !is_key;
+  }
+  return false; // the cell's words ran out with a container open
+}
+
+// the text of root r: a scalar from the cell itself, a located container from its sub-tape.  -> its status; the length in sink.at (0 with a status)
+template <bool FILL>
+__device__ __forceinline__ u32 serialize_root(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table, u32 m, u32 t, u64 v,
+                                              u64 *strip, json_sink<FILL> &sink) {
+  bool ok = true;
+  if (m > ROWS_SPECIAL) {
+    return rows_code(m);
+  } else if (m == ROWS_SPECIAL) {
+    if (t == '"') {
+      const u64 at = v & LOW32, len = v >> 32;
+      ok = at + len <= string_bytes;
+      if (ok) { sink.put_string(sbuf + at, u32(len)); }
+    } else if (t == 'l' || t == 'u' || t == 'd') {
+      ok = t != 'd' || dtoa_is_finite(v);
+      if (ok) { sink.put_number(t, v); }
+    } else {
+      sink.put_literal(t);
+    }
+  } else {
+    const uint4 a = *reinterpret_cast<const uint4 *>(table + m), b = *reinterpret_cast<const uint4 *>(table + m + 1u);
+    const u64 base = a.z, doc_end = b.z, str_base = a.w, str_end = b.w;
+    const u64 low = v & LOW32, high = v >> 32;
+    ok = high <= doc_end && walk_cell<FILL>(tape, sbuf, low, high, base, str_base, str_end, strip, sink);
+  }
+  if (!ok) {
+    sink.at = 0;
+    return QUERY_NO_SUCH_FIELD;
+  }
+  return 0;
+}
+
+// grid: at most JSON_MAX_WORKGROUPS workgroups; lane = cell, grid-stride.  offsets[r] = the low 32 bits of cell r's length, offsets[rows] = 0, status[r];
+// block_sums[workgroup] = the lengths of its cells in 64 bits
+__global__ __launch_bounds__(JSON_THREADS) void k_json_count(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table,
+                                                             const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where, u32 rows,
+                                                             u64 *__restrict__ strips, u32 *__restrict__ offsets, u8 *__restrict__ status, u64 *__restrict__ block_sums) {
+  __shared__ u64 s_sum[JSON_THREADS / 64];
+  const u64 lane_global = u64(blockIdx.x) * JSON_THREADS + threadIdx.x, stride = u64(gridDim.x) * JSON_THREADS;
+  u64 *strip = strips + lane_global * JSON_STRIP_WORDS;
+  u64 sum = 0;
+  for (u64 r = lane_global; r < rows; r += stride) {
+    json_sink<false> sink = {nullptr, 0, 0};
+    const u32 code = serialize_root<false>(tape, sbuf, string_bytes, table, where[r], root_tag[r], root_value[r], strip, sink);
+    offsets[r] = u32(sink.at);
+    status[r] = u8(code);
+    sum += sink.at;
+    if (r == 0) { offsets[rows] = 0; } // the scan's last entry: the total lands there
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m); }
+  if (lane_id() == 0) { s_sum[threadIdx.x >> 6] = sum; }
+  lds_writes_done();
+  __syncthreads();
+  if (threadIdx.x == 0) { block_sums[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]; }
+}
+
+// the same grid.  The bytes of cell r are chars[offsets[r] .. offsets[r + 1]): only a served cell has any
+__global__ __launch_bounds__(JSON_THREADS) void k_json_fill(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table,
+                                                            const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where, u32 rows,
+                                                            u64 *__restrict__ strips, const u32 *__restrict__ offsets, u8 *__restrict__ chars) {
+  const u64 lane_global = u64(blockIdx.x) * JSON_THREADS + threadIdx.x, stride = u64(gridDim.x) * JSON_THREADS;
+  u64 *strip = strips + lane_global * JSON_STRIP_WORDS;
+  for (u64 r = lane_global; r < rows; r += stride) {
+    const u64 begin = offsets[r], end = offsets[r + 1u];
+    if (begin >= end) { continue; }
+    json_sink<true> sink = {chars + begin, end - begin, 0};
+    (void)serialize_root<true>(tape, sbuf, string_bytes, table, where[r], root_tag[r], root_value[r], strip, sink);
+  }
+}
+
+static inline u32 json_blocks(u32 rows) {
+  const u64 all = (u64(rows) + JSON_THREADS - 1) / JSON_THREADS;
+  return u32(all < JSON_MAX_WORKGROUPS ? all : JSON_MAX_WORKGROUPS);
+}
+static inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// [ctrl, 256 bytes][the count's block sums][the scan's block sums][the lanes' strips]
+struct json_workspace {
+  count_total_dev *ctrl;
+  u64 *block_sums, *strips;
+  int *partial;
+  size_t bytes;
+};
+static inline json_workspace carve_json_workspace(void *base, u32 rows) {
+  uint8_t *p = static_cast<uint8_t *>(base);
+  const u32 blocks = json_blocks(rows);
+  json_workspace w;
+  size_t at = 0;
+  w.ctrl = reinterpret_cast<count_total_dev *>(p + at);  at += 256;
+  w.block_sums = reinterpret_cast<u64 *>(p + at);        at += up256(size_t(blocks) * sizeof(u64));
+  w.partial = reinterpret_cast<int *>(p + at);           at += up256((size_t((u64(rows) + 1 + 4095) / 4096) + 64) * sizeof(int));
+  w.strips = reinterpret_cast<u64 *>(p + at);            at += up256(size_t(blocks) * JSON_THREADS * JSON_STRIP_WORDS * sizeof(u64));
+  w.bytes = at;
+  return w;
+}
+
+} // namespace
+
+size_t json_workspace_bytes(uint32_t rows) { return carve_json_workspace(nullptr, rows).bytes; }
+
+const count_total_dev *launch_json_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value,
+                                         const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s) {
+  const json_workspace w = carve_json_workspace(workspace, rows);
+  const u32 blocks = json_blocks(rows);
+  launch_rows_locate(tape, table, docs, root_value, root_tag, rows, where, s);
+  hipLaunchKernelGGL(k_json_count, dim3(blocks), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag, static_cast<const u32 *>(where), rows, w.strips,
+                     offsets, status, w.block_sums);
+  launch_count_total(w.block_sums, blocks, rows, w.ctrl, s);
+  enqueue_scan(reinterpret_cast<int *>(offsets), rows + 1u, &w.ctrl->n_plus_1, w.partial, s);
+  return w.ctrl;
+}
+
+void launch_json_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                      uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s) {
+  const json_workspace w = carve_json_workspace(workspace, rows);
+  hipLaunchKernelGGL(k_json_fill, dim3(json_blocks(rows)), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag, where, rows, w.strips, offsets, chars);
+}
+
+} // namespace sjgpu

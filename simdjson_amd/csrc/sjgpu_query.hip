@@ -761,13 +761,11 @@ __global__ __launch_bounds__(QUERY_THREADS) void k_wide_emit(const u64 *__restri
 //   ROWS_SPECIAL | (code - 16)   every pointer answers `code` (a failed root keeps its 17 / 19 / 20 / 22; a tag that is none, or a container cell that disagrees
 //                                with the tape, is NO_SUCH_FIELD)
 // (docs is below 0xFFFFFFF0: the C-ABI refuses more.)
-constexpr u32 ROWS_SPECIAL = 0xFFFFFFF0u;
+// (ROWS_SPECIAL and rows_code: sjgpu_internal.h -- sjgpu_json.hip reads the same verdicts)
 
 __device__ __forceinline__ bool is_query_code(u32 t) {
   return t == QUERY_INCORRECT_TYPE || t == QUERY_INDEX_OUT_OF_BOUNDS || t == QUERY_NO_SUCH_FIELD || t == QUERY_INVALID_JSON_POINTER;
 }
-// the code of a verdict above ROWS_SPECIAL
-__device__ __forceinline__ u32 rows_code(u32 m) { return (m & 15u) + 16u; }
 
 // one lane per root.  A container cell is followed only when its opening index c lies INSIDE a document (behind its root word), the word there carries the
 // cell's tag and points where the cell's high half says: log2(docs) table reads, one tape word.
@@ -1116,6 +1114,17 @@ void launch_object_fields_fill(const uint64_t *tape, const uint8_t *string_buf, 
                                const uint32_t *offsets, uint64_t *key_value, uint8_t *key_tag, uint64_t *value, uint8_t *tag, hipStream_t s) {
   hipLaunchKernelGGL(k_object_fields_fill, dim3(blocks_of(rows, QUERY_THREADS)), dim3(QUERY_THREADS), 0, s, tape, string_buf, table, root_value, where, rows, offsets, key_value,
                      key_tag, value, tag);
+}
+
+// what the units beside this one share of it (sjgpu_json.hip): the roots' verdicts, and the 64-bit total of a count kernel's block sums with the scan's length
+void launch_rows_locate(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows, uint32_t *where,
+                        hipStream_t s) {
+  hipLaunchKernelGGL(k_rows_locate, dim3(blocks_of(rows, QUERY_THREADS)), dim3(QUERY_THREADS), 0, s, tape, table, docs, root_value, root_tag, rows, where);
+}
+
+void launch_count_total(const uint64_t *block_sums, uint32_t blocks, uint32_t entries, count_total_dev *ctrl, hipStream_t s) {
+  static_assert(sizeof(count_total_dev) == sizeof(gather_ctrl), "one control block");
+  hipLaunchKernelGGL(k_gather_total, dim3(1), dim3(QUERY_THREADS), 0, s, block_sums, blocks, entries, reinterpret_cast<gather_ctrl *>(ctrl));
 }
 
 void launch_cell_sizes(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows, uint32_t *where,
