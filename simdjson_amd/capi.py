@@ -91,6 +91,21 @@ SJGPU_E_INTERNAL = -7  # (include/sjgpu_dict.h) a bounded loop of the library ra
 JSON_EXPORTS = ["sjgpu_serialize_cells_device"]
 
 
+# what include/sjgpu_write.h declares (typed columns as JSON records: one object per row into offsets + chars); the bindings are the free functions of
+# simdjson_amd/writer.py
+WRITE_EXPORTS = ["sjgpu_write_records_device"]
+# SJGPU_COL_*: what a column of sjgpu_write_records_device holds (1 .. 4 are SJGPU_GET_INT64 .. SJGPU_GET_BOOL)
+COL_INT64, COL_UINT64, COL_DOUBLE, COL_BOOL, COL_STRING, COL_JSON, COL_STRING_CELLS = 1, 2, 3, 4, 5, 8, 9
+WRITE_OMIT_NULLS, WRITE_NEWLINE = 1, 2
+INDEX_OUT_OF_BOUNDS = 19  # the status of a row with a string or JSON cell outside its column's characters
+
+
+class WriteColumn(ctypes.Structure):
+    """sjgpu_write_column"""
+    _fields_ = [("key", ctypes.c_void_p), ("key_len", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("values_dev", ctypes.c_void_p), ("valid_dev", ctypes.c_void_p),
+                ("offsets_dev", ctypes.c_void_p), ("chars_dev", ctypes.c_void_p), ("chars_bytes", ctypes.c_uint64)]
+
+
 def infer_getters(kinds):
     """The getter a loader would ask of each row, from its census (kinds: K x 16 counts as sjgpu_cell_kinds_device leaves them) -> list of K SJGPU_GET_* or 0.
     The ELEMENTS of a row are its cells except the nulls and the codes 17 / 19 / 20 / 22 (they become invalid bits under any getter):
@@ -235,6 +250,8 @@ def load_library():
     L.sjgpu_cell_kinds_by_code_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     L.sjgpu_serialize_cells_device.restype = ctypes.c_int
     L.sjgpu_serialize_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, u64p]
+    L.sjgpu_write_records_device.restype = ctypes.c_int
+    L.sjgpu_write_records_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, u64p]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int

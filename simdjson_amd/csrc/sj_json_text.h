@@ -104,5 +104,69 @@ SJ_HD u64 escape_write(const u8 *s, u32 len, u8 *out, u64 room) {
   return at + 1u;
 }
 
+// s[0 .. len) as it is to out[0 .. len), no byte at or beyond out + room -> len.  Eight bytes at a time while they fit, as escape_write moves them
+SJ_HD u64 raw_write(const u8 *s, u64 len, u8 *out, u64 room) {
+  const u64 n = len < room ? len : room;
+  u64 i = 0;
+  for (; i + 8u <= n; i += 8u) {
+    const u64 w = load8(s + i);
+    __builtin_memcpy(out + i, &w, 8);
+  }
+  for (; i < n; i++) { out[i] = s[i]; }
+  return len;
+}
+
+// Where one writer of text writes: out[0 .. room), `at` counts on beyond it.  FILL = false is the count pass: nothing is stored, `at` is the length.
+// (the sink of sjgpu_write.hip; sjgpu_json.hip keeps the one it was measured with)
+template <bool FILL>
+struct text_sink {
+  u8 *out;
+  u64 room, at;
+  SJ_HD void put(u32 c) {
+    if (FILL && at < room) { out[at] = u8(c); }
+    at++;
+  }
+  SJ_HD void put_null() { put('n'); put('u'); put('l'); put('l'); }
+  SJ_HD void put_bool(bool v) {
+    if (v) {
+      put('t'); put('r'); put('u'); put('e');
+    } else {
+      put('f'); put('a'); put('l'); put('s'); put('e');
+    }
+  }
+  // what: 0 an int64, 1 a uint64, 2 a finite double, each as its 64 bits
+  SJ_HD void put_number(u32 what, u64 v) {
+    u32 length = 0;
+    const bool fits = FILL && at + DTOA_MAX_BYTES <= room; // (24 >= the 20 of an integer)
+    if (!fits) { length = what == 2u ? dtoa_length(v) : what == 0u ? int64_text_length(v) : decimal_digits(v); }
+    if (FILL && (fits || at + length <= room)) {
+      u8 *p = out + at;
+      if (what == 2u) {
+        length = dtoa_write(v, p);
+      } else if (what == 0u) {
+        length = int64_text_write(v, p);
+      } else {
+        length = decimal_digits(v);
+        write_decimal(p, v, length);
+      }
+    }
+    at += length;
+  }
+  SJ_HD void put_string(const u8 *s, u32 len) {
+    if (FILL) {
+      at += escape_write(s, len, out + (at < room ? at : room), at < room ? room - at : 0u);
+    } else {
+      at += escaped_length(s, len);
+    }
+  }
+  SJ_HD void put_raw(const u8 *s, u64 len) {
+    if (FILL) {
+      at += raw_write(s, len, out + (at < room ? at : room), at < room ? room - at : 0u);
+    } else {
+      at += len;
+    }
+  }
+};
+
 } // namespace sjgpu
 #endif

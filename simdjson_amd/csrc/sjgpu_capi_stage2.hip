@@ -10,7 +10,9 @@
 #include "sjgpu_fields.h"
 #include "sjgpu_dict.h"
 #include "sjgpu_json.h"
+#include "sjgpu_write.h"
 #include "sj_path_program.h"
+#include "sj_write_table.h"
 
 extern "C" {
 
@@ -766,6 +768,63 @@ int sjgpu_serialize_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t 
     launch_json_fill(tape, sbuf, string_bytes, table, root_value, root_tag, rows, where, offsets, static_cast<uint8_t *>(chars_dev), ctx->d_tmp, s);
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s)); // (the verdicts and the workspace are free again when the call returns)
+  }
+  return 0;
+}
+
+// ---- typed columns as JSON records (k_write_count, k_write_fill in sjgpu_write.hip; include/sjgpu_write.h) -------------------------------------------------
+// The serializer's shape: the count's total read back, the fill only when it fits.  The column table and the escaped keys (sj_write_table.h) go up through the
+// context's block as the compiled pointers of sjgpu_at_pointers_device do -- behind the same wait for the block's previous user --; the call ends with the stream
+// drained on every road, so the block is free again when it returns and no event is recorded
+int sjgpu_write_records_device(sjgpu_ctx *ctx, const sjgpu_write_column *columns, uint32_t K, uint32_t n, uint32_t flags, void *offsets_dev, void *status_dev, void *chars_dev,
+                               uint64_t chars_cap, void *counts_dev, void *stream, uint64_t *bytes_out) {
+  if (bytes_out) { *bytes_out = 0; }
+  if (!ctx || !offsets_dev || !counts_dev || !bytes_out || (n && !status_dev) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
+  if ((reinterpret_cast<uintptr_t>(offsets_dev) & 3u) || (reinterpret_cast<uintptr_t>(counts_dev) & 7u)) { return SJGPU_E_BADARG; }
+  write_table table;
+  if (!make_write_table(columns, K, n, flags, &table)) { return SJGPU_E_BADARG; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = pick(ctx, stream);
+  if (n == 0) {
+    SJ_TRY(ctx, hipMemsetAsync(offsets_dev, 0, sizeof(uint32_t), s));
+    SJ_TRY(ctx, hipMemsetAsync(counts_dev, 0, 4 * sizeof(uint64_t), s));
+    SJ_TRY(ctx, hipStreamSynchronize(s));
+    return 0;
+  }
+  if (ctx->query_in_flight) { // the block is the context's: the walk of the previous call must have read it
+    SJ_TRY(ctx, hipEventSynchronize(ctx->ev_query));
+    ctx->query_in_flight = false;
+  }
+  const size_t block = 256 + table.bytes.size(); // (the block's first 256 bytes are the table check's in the query calls: left alone here)
+  int rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, block);
+  if (rc) { return rc; }
+  rc = ensure_tmp(ctx, write_workspace_bytes(n));
+  if (rc) { return rc; }
+  if (ctx->h_query_bytes < block) {
+    if (ctx->h_query) { (void)hipHostFree(ctx->h_query); ctx->h_query = nullptr; ctx->h_query_bytes = 0; }
+    SJ_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_query), block, hipHostMallocDefault));
+    ctx->h_query_bytes = block;
+  }
+  if (!table.bytes.empty()) {
+    std::memcpy(ctx->h_query + 256, table.bytes.data(), table.bytes.size());
+    SJ_TRY(ctx, hipMemcpyAsync(ctx->d_query + 256, ctx->h_query + 256, table.bytes.size(), hipMemcpyHostToDevice, s));
+  }
+  const write_column_dev *cols = reinterpret_cast<const write_column_dev *>(ctx->d_query + 256);
+  const uint8_t *keys = ctx->d_query + 256 + table.keys_at;
+  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  const count_total_dev *total_dev = launch_write_count(cols, keys, K, n, flags, offsets, static_cast<uint8_t *>(status_dev), static_cast<uint64_t *>(counts_dev), ctx->d_tmp, s);
+  SJ_TRY(ctx, hipGetLastError());
+  uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
+  SJ_TRY(ctx, hipMemcpyAsync(total, &total_dev->total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  const uint64_t bytes = *total;
+  *bytes_out = bytes;
+  if (bytes > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
+  if (bytes > chars_cap) { return SJGPU_E_OVERFLOW; }
+  if (bytes) {
+    launch_write_fill(cols, keys, K, n, flags, offsets, static_cast<uint8_t *>(chars_dev), s);
+    SJ_TRY(ctx, hipGetLastError());
+    SJ_TRY(ctx, hipStreamSynchronize(s)); // (the block and the workspace are free again when the call returns)
   }
   return 0;
 }

@@ -420,6 +420,28 @@ const count_total_dev *launch_json_count(const uint64_t *tape, const uint8_t *st
                                          const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s);
 void launch_json_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
                       uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s);
+// ---- typed columns as JSON records (sjgpu_write.hip: sjgpu_write_records_device, include/sjgpu_write.h) -----------------------------------------------------
+// One column as the kernels read it, K of them in device memory (sj_write_table.h makes them from the caller's sjgpu_write_column and escapes the keys):
+// key_at / key_len: the column's escaped "key": prefix inside the `keys` bytes.
+struct write_column_dev {
+  const uint64_t *values, *valid;
+  const uint32_t *offsets;
+  const uint8_t *chars;
+  uint64_t chars_bytes;
+  uint32_t kind, key_at, key_len, pad;
+};
+constexpr uint32_t WRITE_MAX_COLUMNS = 64, WRITE_MAX_KEY = 1024, WRITE_MAX_PREFIXES = 8192;
+// n >= 1, n + 1 entries the scan takes; cols[0 .. K) and keys in device memory; workspace: write_workspace_bytes(n), 256-byte aligned.  launch_write_count: status[r],
+// the four counts (zeroed here, on the same stream) and, in offsets[0 .. n], the exclusive sum of the rows' text lengths -> where the 64-bit total lies.
+// launch_write_fill, when the total fits: the bytes of row r to chars[offsets[r] .. offsets[r + 1]), never beyond
+size_t write_workspace_bytes(uint32_t n);
+const count_total_dev *launch_write_count(const write_column_dev *cols, const uint8_t *keys, uint32_t K, uint32_t n, uint32_t flags, uint32_t *offsets, uint8_t *status,
+                                          uint64_t *counts, void *workspace, hipStream_t s);
+void launch_write_fill(const write_column_dev *cols, const uint8_t *keys, uint32_t K, uint32_t n, uint32_t flags, const uint32_t *offsets, uint8_t *chars, hipStream_t s);
+// the rows one workgroup iteration takes, the grid's cap and the LDS window of the staged road, for the tests that stand on their edges
+uint32_t write_rows_per_step();
+uint32_t write_max_workgroups();
+uint32_t write_window_bytes();
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);
