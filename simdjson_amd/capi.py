@@ -106,6 +106,17 @@ class WriteColumn(ctypes.Structure):
                 ("offsets_dev", ctypes.c_void_p), ("chars_dev", ctypes.c_void_p), ("chars_bytes", ctypes.c_uint64)]
 
 
+# what include/sjgpu_nested.h declares (list columns and array rows as nested JSON: the writer above with list fields, array rows and bare values); the bindings are
+# free functions of simdjson_amd/writer.py too
+NESTED_EXPORTS = ["sjgpu_write_nested_device"]
+WRITE_ARRAY_ROWS, WRITE_BARE = 4, 8
+
+
+class WriteField(ctypes.Structure):
+    """sjgpu_write_field"""
+    _fields_ = [("col", WriteColumn), ("list_offsets_dev", ctypes.c_void_p), ("list_valid_dev", ctypes.c_void_p), ("elements", ctypes.c_uint64)]
+
+
 def infer_getters(kinds):
     """The getter a loader would ask of each row, from its census (kinds: K x 16 counts as sjgpu_cell_kinds_device leaves them) -> list of K SJGPU_GET_* or 0.
     The ELEMENTS of a row are its cells except the nulls and the codes 17 / 19 / 20 / 22 (they become invalid bits under any getter):
@@ -252,6 +263,8 @@ def load_library():
     L.sjgpu_serialize_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_write_records_device.restype = ctypes.c_int
     L.sjgpu_write_records_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, u64p]
+    L.sjgpu_write_nested_device.restype = ctypes.c_int
+    L.sjgpu_write_nested_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, u64p]
     L.sjgpu_comm_unique_id.restype = ctypes.c_int
     L.sjgpu_comm_unique_id.argtypes = [vp, sz]
     L.sjgpu_comm_create.restype = ctypes.c_int

@@ -13,6 +13,7 @@
 #include "sjgpu_write.h"
 #include "sj_path_program.h"
 #include "sj_write_table.h"
+#include "sj_nested_table.h"
 
 extern "C" {
 
@@ -776,18 +777,14 @@ int sjgpu_serialize_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t 
 // The serializer's shape: the count's total read back, the fill only when it fits.  The column table and the escaped keys (sj_write_table.h) go up through the
 // context's block as the compiled pointers of sjgpu_at_pointers_device do -- behind the same wait for the block's previous user --; the call ends with the stream
 // drained on every road, so the block is free again when it returns and no event is recorded
-int sjgpu_write_records_device(sjgpu_ctx *ctx, const sjgpu_write_column *columns, uint32_t K, uint32_t n, uint32_t flags, void *offsets_dev, void *status_dev, void *chars_dev,
-                               uint64_t chars_cap, void *counts_dev, void *stream, uint64_t *bytes_out) {
-  if (bytes_out) { *bytes_out = 0; }
-  if (!ctx || !offsets_dev || !counts_dev || !bytes_out || (n && !status_dev) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
-  if ((reinterpret_cast<uintptr_t>(offsets_dev) & 3u) || (reinterpret_cast<uintptr_t>(counts_dev) & 7u)) { return SJGPU_E_BADARG; }
-  write_table table;
-  if (!make_write_table(columns, K, n, flags, &table)) { return SJGPU_E_BADARG; }
+// (shared with sjgpu_write_nested_device: `nested` says whose table this is -- write_field_dev and six counts, or write_column_dev and four)
+static int write_through_block(sjgpu_ctx *ctx, const write_table &table, bool nested, uint32_t K, uint32_t n, uint32_t flags, void *offsets_dev, void *status_dev,
+                               void *chars_dev, uint64_t chars_cap, void *counts_dev, void *stream, uint64_t *bytes_out) {
   SJ_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = pick(ctx, stream);
   if (n == 0) {
     SJ_TRY(ctx, hipMemsetAsync(offsets_dev, 0, sizeof(uint32_t), s));
-    SJ_TRY(ctx, hipMemsetAsync(counts_dev, 0, 4 * sizeof(uint64_t), s));
+    SJ_TRY(ctx, hipMemsetAsync(counts_dev, 0, (nested ? 6 : 4) * sizeof(uint64_t), s));
     SJ_TRY(ctx, hipStreamSynchronize(s));
     return 0;
   }
@@ -810,9 +807,12 @@ int sjgpu_write_records_device(sjgpu_ctx *ctx, const sjgpu_write_column *columns
     SJ_TRY(ctx, hipMemcpyAsync(ctx->d_query + 256, ctx->h_query + 256, table.bytes.size(), hipMemcpyHostToDevice, s));
   }
   const write_column_dev *cols = reinterpret_cast<const write_column_dev *>(ctx->d_query + 256);
+  const write_field_dev *fields = reinterpret_cast<const write_field_dev *>(ctx->d_query + 256);
   const uint8_t *keys = ctx->d_query + 256 + table.keys_at;
   uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
-  const count_total_dev *total_dev = launch_write_count(cols, keys, K, n, flags, offsets, static_cast<uint8_t *>(status_dev), static_cast<uint64_t *>(counts_dev), ctx->d_tmp, s);
+  const count_total_dev *total_dev =
+      nested ? launch_nested_count(fields, keys, K, n, flags, offsets, static_cast<uint8_t *>(status_dev), static_cast<uint64_t *>(counts_dev), ctx->d_tmp, s)
+             : launch_write_count(cols, keys, K, n, flags, offsets, static_cast<uint8_t *>(status_dev), static_cast<uint64_t *>(counts_dev), ctx->d_tmp, s);
   SJ_TRY(ctx, hipGetLastError());
   uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
   SJ_TRY(ctx, hipMemcpyAsync(total, &total_dev->total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -822,11 +822,37 @@ int sjgpu_write_records_device(sjgpu_ctx *ctx, const sjgpu_write_column *columns
   if (bytes > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
   if (bytes > chars_cap) { return SJGPU_E_OVERFLOW; }
   if (bytes) {
-    launch_write_fill(cols, keys, K, n, flags, offsets, static_cast<uint8_t *>(chars_dev), s);
+    if (nested) {
+      launch_nested_fill(fields, keys, K, n, flags, offsets, static_cast<uint8_t *>(chars_dev), s);
+    } else {
+      launch_write_fill(cols, keys, K, n, flags, offsets, static_cast<uint8_t *>(chars_dev), s);
+    }
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s)); // (the block and the workspace are free again when the call returns)
   }
   return 0;
+}
+
+int sjgpu_write_records_device(sjgpu_ctx *ctx, const sjgpu_write_column *columns, uint32_t K, uint32_t n, uint32_t flags, void *offsets_dev, void *status_dev, void *chars_dev,
+                               uint64_t chars_cap, void *counts_dev, void *stream, uint64_t *bytes_out) {
+  if (bytes_out) { *bytes_out = 0; }
+  if (!ctx || !offsets_dev || !counts_dev || !bytes_out || (n && !status_dev) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
+  if ((reinterpret_cast<uintptr_t>(offsets_dev) & 3u) || (reinterpret_cast<uintptr_t>(counts_dev) & 7u)) { return SJGPU_E_BADARG; }
+  write_table table;
+  if (!make_write_table(columns, K, n, flags, &table)) { return SJGPU_E_BADARG; }
+  return write_through_block(ctx, table, false, K, n, flags, offsets_dev, status_dev, chars_dev, chars_cap, counts_dev, stream, bytes_out);
+}
+
+// ---- list columns and array rows as nested JSON (k_nested_count, k_nested_fill in sjgpu_write.hip; include/sjgpu_nested.h) -------------------------------------
+// The plain writer's call over the field table of sj_nested_table.h: the same block, the same waits, the same workspace
+int sjgpu_write_nested_device(sjgpu_ctx *ctx, const sjgpu_write_field *fields, uint32_t K, uint32_t n, uint32_t flags, void *offsets_dev, void *status_dev, void *chars_dev,
+                              uint64_t chars_cap, void *counts_dev, void *stream, uint64_t *bytes_out) {
+  if (bytes_out) { *bytes_out = 0; }
+  if (!ctx || !offsets_dev || !counts_dev || !bytes_out || (n && !status_dev) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
+  if ((reinterpret_cast<uintptr_t>(offsets_dev) & 3u) || (reinterpret_cast<uintptr_t>(counts_dev) & 7u)) { return SJGPU_E_BADARG; }
+  write_table table;
+  if (!make_nested_table(fields, K, n, flags, &table)) { return SJGPU_E_BADARG; }
+  return write_through_block(ctx, table, true, K, n, flags, offsets_dev, status_dev, chars_dev, chars_cap, counts_dev, stream, bytes_out);
 }
 
 // ---- typed getters over cells (k_cell_kinds, k_cast_cells in sjgpu_cast.hip; include/sjgpu_cast.h) ------------------------------------------------------

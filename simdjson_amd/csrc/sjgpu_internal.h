@@ -442,6 +442,19 @@ void launch_write_fill(const write_column_dev *cols, const uint8_t *keys, uint32
 uint32_t write_rows_per_step();
 uint32_t write_max_workgroups();
 uint32_t write_window_bytes();
+// ---- list columns and array rows as nested JSON (sjgpu_write.hip: sjgpu_write_nested_device, include/sjgpu_nested.h) ----------------------------------------
+// One field as the kernels read it (sj_nested_table.h makes them from the caller's sjgpu_write_field): list_offsets == nullptr: `col` is a plain column over the
+// rows; otherwise `col` is the ELEMENTS, `elements` of them, and row r's list is list_offsets[r] .. list_offsets[r + 1]
+struct write_field_dev {
+  write_column_dev col;
+  const uint32_t *list_offsets;
+  const uint64_t *list_valid;
+  uint64_t elements;
+};
+// as launch_write_count / launch_write_fill, with the same workspace (write_workspace_bytes(n)); SIX counts
+const count_total_dev *launch_nested_count(const write_field_dev *fields, const uint8_t *keys, uint32_t K, uint32_t n, uint32_t flags, uint32_t *offsets, uint8_t *status,
+                                           uint64_t *counts, void *workspace, hipStream_t s);
+void launch_nested_fill(const write_field_dev *fields, const uint8_t *keys, uint32_t K, uint32_t n, uint32_t flags, const uint32_t *offsets, uint8_t *chars, hipStream_t s);
 // On-Demand's raw key comparison over the whole list (sjgpu_strings.hip); names_block: [u32 lens[K]][name bytes back to back] in device memory
 void launch_match_keys(const uint8_t *buf, uint64_t len, const uint32_t *idx, uint32_t n, const uint8_t *names_block, uint32_t K, uint32_t *out, uint32_t *matches,
                        hipStream_t s);
