@@ -44,6 +44,10 @@ class Doc(ctypes.Structure):
                 ("n", ctypes.c_uint32), ("error", ctypes.c_int)]
 
 
+# what include/sjgpu_debug.h declares (diagnostics of the single-pass workspace: an extension of the C-ABI with a header of its own)
+DEBUG_EXPORTS = ["sjgpu_debug_read_workspace", "sjgpu_debug_gave_up_count"]
+
+
 # what include/sjgpu_stream.h declares (document streams: an extension of the C-ABI with a header of its own)
 STREAM_EXPORTS = ["sjgpu_stage2_many_device", "sjgpu_parse_many"]
 # sjgpu_doc_span (include/sjgpu_stream.h): one entry of the document table of sjgpu_stage2_many_device / sjgpu_parse_many
@@ -210,6 +214,10 @@ def load_library():
     L.sjgpu_debug_trace_stage1.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint32]
     L.sjgpu_debug_string_path.restype = ctypes.c_int
     L.sjgpu_debug_string_path.argtypes = [vp]
+    L.sjgpu_debug_read_workspace.restype = ctypes.c_int
+    L.sjgpu_debug_read_workspace.argtypes = [vp, ctypes.POINTER(ScanResult), vp, sz, ctypes.POINTER(sz)]
+    L.sjgpu_debug_gave_up_count.restype = ctypes.c_uint64
+    L.sjgpu_debug_gave_up_count.argtypes = [vp]
     L.sjgpu_debug_trace_pipelined.restype = ctypes.c_int
     L.sjgpu_debug_trace_pipelined.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint32, u32p]
     L.sjgpu_stage1_many.restype = ctypes.c_int
@@ -982,6 +990,23 @@ class DomParserImplementation:
         if rc != 0:
             raise SjgpuError(f"sjgpu_debug_trace_stage1 error {rc}: {self.last_error()}")
         return out
+
+    def read_workspace(self):
+        """sjgpu_debug_read_workspace -> ((n, flags, out_len) as the device holds them, uint64[words allocated]: the single-pass workspace,
+        [tile descriptors][control words], which every single-pass kernel leaves all zero.  Waits for the device; changes nothing."""
+        r = ScanResult()
+        words = ctypes.c_size_t(0)
+        rc = self.L.sjgpu_debug_read_workspace(self.h, ctypes.byref(r), None, 0, ctypes.byref(words))
+        out = np.zeros(int(words.value), dtype=np.uint64)
+        if rc == 0 and len(out):
+            rc = self.L.sjgpu_debug_read_workspace(self.h, ctypes.byref(r), out.ctypes.data, len(out), ctypes.byref(words))
+        if rc != 0 or int(words.value) != len(out):
+            raise SjgpuError(f"sjgpu_debug_read_workspace error {rc}: {self.last_error()}")
+        return (int(r.n), int(r.flags), int(r.out_len)), out
+
+    def gave_up_count(self):
+        """sjgpu_debug_gave_up_count: results with F_INTERNAL this context has read since it was created or taken from the pool"""
+        return int(self.L.sjgpu_debug_gave_up_count(self.h))
 
     def set_pipeline(self, pipeline="auto"):
         """"split" | "fused" | "auto" (also accepts True = fused / False = split)."""

@@ -2,6 +2,7 @@
 // sjgpu_capi_host.hip, sjgpu_capi_stage2.hip; what they share: sjgpu_ctx.h).  No CPU compute path exists here: if HIP is unusable every entry point returns a
 // negative code.
 #include "sjgpu_ctx.h"
+#include "sjgpu_debug.h"
 
 
 extern "C" {
@@ -135,6 +136,7 @@ extern "C" int sjgpu_ctx_create(int device, size_t capacity, sjgpu_ctx **out) {
     ctx->pending_scan_bytes = 0;
     ctx->last_pipeline = 0;
     ctx->last_kernel = "";
+    ctx->gave_up = 0;
     ctx->err[0] = 0;
     *out = ctx;
     return 0;
@@ -425,6 +427,35 @@ int sjgpu_debug_trace_pipelined(sjgpu_ctx *ctx, const void *buf_dev, size_t len,
   if (e != hipSuccess) { return fail(ctx, e, "debug_trace_pipelined"); }
   return *workgroups_out ? 0 : SJGPU_E_BADARG;
 }
+
+// Reads, never writes: no allocation, ws_dirty and the next call's road stay as they are.  Waits for the whole device, since the calls run on the callers' streams.
+int sjgpu_debug_read_workspace(sjgpu_ctx *ctx, sjgpu_scan_result *result_out, uint64_t *words_host, size_t cap_words, size_t *words_out) {
+  if (!ctx || !result_out || !words_out || (cap_words && !words_host)) { return SJGPU_E_BADARG; }
+  *words_out = 0;
+  result_out->n = 0;
+  result_out->flags = 0;
+  result_out->out_len = 0;
+  if (!ctx->d_result) { return 0; }
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) { e = hipDeviceSynchronize(); }
+  scan_result_dev r{};
+  if (e == hipSuccess) { e = hipMemcpy(&r, ctx->d_result, sizeof r, hipMemcpyDeviceToHost); }
+  const size_t words = size_t(ctx->ws_capacity ? num_fused_tiles(ctx->ws_capacity) : 0) + FUSED_WORKSPACE_EXTRA_WORDS;
+  const size_t take = words < cap_words ? words : cap_words;
+  if (e == hipSuccess && take) { e = hipMemcpy(words_host, ctx->desc, take * sizeof(uint64_t), hipMemcpyDeviceToHost); }
+  if (e != hipSuccess) { // (not fail(): that marks the workspace dirty, and this call changes nothing)
+    (void)hipGetLastError();
+    std::snprintf(ctx->err, sizeof ctx->err, "debug_read_workspace: %s", hipGetErrorString(e));
+    return SJGPU_E_HIP;
+  }
+  result_out->n = r.n;
+  result_out->flags = r.flags;
+  result_out->out_len = r.out_len;
+  *words_out = words;
+  return 0;
+}
+
+uint64_t sjgpu_debug_gave_up_count(const sjgpu_ctx *ctx) { return ctx ? ctx->gave_up : 0; }
 
 int sjgpu_set_pipeline(sjgpu_ctx *ctx, int pipeline) {
   if (!ctx || pipeline < 0 || pipeline > 2) { return SJGPU_E_BADARG; }

@@ -307,6 +307,7 @@ int span_advance(sjgpu_ctx *ctx, sjgpu_ctx::span_slot &sl, bool blocking) {
     else if (hipEventQuery(sl.ev) != hipSuccess) { (void)hipGetLastError(); return 0; }
     sl.n = sl.h_res->n;
     const uint32_t flags = sl.h_res->flags;
+    note_result_flags(ctx, flags); // (the span was scanned on the split pipeline, which cannot give up: counted all the same, like every result read)
     // a control character inside a string or broken UTF-8 SOMEWHERE in the span says nothing about a particular window
     sl.usable = (flags & (SJGPU_F_UNESCAPED_CTRL | SJGPU_F_UTF8_ERROR | SJGPU_F_INTERNAL | SJGPU_F_IDX_OVERFLOW)) == 0;
     if (size_t(sl.n) + 8 > sl.h_words) {

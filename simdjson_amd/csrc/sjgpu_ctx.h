@@ -150,6 +150,7 @@ struct sjgpu_ctx {
   // the device says whether that kernel ran to its end.  Whatever makes that doubtful -- a HIP error recorded on this context (fail()), a chain that gave
   // up (SJGPU_F_INTERNAL), a traced run -- sets this, and the next single-pass call clears the workspace in front of its kernel instead of trusting it.
   bool ws_dirty = false;
+  uint64_t gave_up = 0;       // results carrying SJGPU_F_INTERNAL this context has fetched since it was created or un-parked (sjgpu_debug_gave_up_count)
   int device_finish = 1;      // streaming-mode finish: 0 host, 1 device beyond the small-document path, 2 always device
   // scratch of the device-side finish / depth scan (sjgpu_finish.hip), grown on demand
   uint8_t *d_tmp = nullptr;
@@ -307,13 +308,18 @@ int ensure_scan_workspace(sjgpu_ctx *ctx, size_t len, bool split) {
 }
 int ensure_result_only(sjgpu_ctx *ctx) { return ctx->d_result ? 0 : alloc_result(ctx, 0); }
 
+// every place that reads a scan's flags off the device comes through here: a chain that gave up is counted, and what its workgroups left behind is not trusted
+void note_result_flags(sjgpu_ctx *ctx, uint32_t flags) {
+  if (flags & SJGPU_F_INTERNAL) { ctx->ws_dirty = true; ctx->gave_up++; }
+}
+
 int fetch_result(sjgpu_ctx *ctx, hipStream_t s, sjgpu_scan_result *out) {
   SJ_TRY(ctx, hipMemcpyAsync(ctx->h_result, ctx->d_result, sizeof(scan_result_dev), hipMemcpyDeviceToHost, s));
   SJ_TRY(ctx, hipStreamSynchronize(s));
   out->n = ctx->h_result->n;
   out->flags = ctx->h_result->flags;
   out->out_len = ctx->h_result->out_len;
-  if (out->flags & SJGPU_F_INTERNAL) { ctx->ws_dirty = true; } // a chain that gave up: do not trust what its workgroups left behind
+  note_result_flags(ctx, out->flags);
   if (ctx->pending_scan_bytes) {
     ctx->density_permille = uint32_t(uint64_t(out->n) * 1000u / ctx->pending_scan_bytes);
     ctx->pending_scan_bytes = 0;

@@ -96,7 +96,15 @@ __device__ __forceinline__ void leave_and_clean(u64 *desc, u32 ntiles, u32 *tick
   lds_writes_done();
   __syncthreads();
   if (sh_last == 0u) { return; }
+#ifdef SJGPU_SELFTEST_LEAVE_DIRTY // tests/test_kernels_emu.py: with one control word left behind -- 1 the second ticket counter, 2 [ticket, done] -- the emulator's look at the workspace must FAIL
+#ifndef SJ_EMU
+#error "SJGPU_SELFTEST_LEAVE_DIRTY is for the emulator build of the CPU tier only: never in a library that runs on a GPU"
+#endif
+  const u32 keep = ntiles + (SJGPU_SELFTEST_LEAVE_DIRTY == 1 ? 16u : 0u);
+  for (u32 i = threadIdx.x; i < ntiles + FUSED_CTL_WORDS; i += THREADS) { if (i != keep) { desc_store(desc + i, 0ull); } }
+#else
   for (u32 i = threadIdx.x; i < ntiles + FUSED_CTL_WORDS; i += THREADS) { desc_store(desc + i, 0ull); }
+#endif
 }
 
 // Wave-wide look-back for tile `tile` (all 64 lanes of ONE wave call this).  On success S = in-string at

@@ -95,6 +95,14 @@ def assert_same_all(p, orc, data, tag="", modes=(0,)):
     assert p.validate_utf8(data) == orc.validate_utf8(data), f"utf8 mismatch {tag}"
 
 
+def assert_workspace_clean(p, tag=""):
+    """The single-pass kernels clear nothing in front of themselves: each trusts that the one before it left [tile descriptors][control words] all zero
+    (sjgpu_fused.hip: leave_and_clean).  Every word of the context's allocation, read off the device (tests/test_gpu_workspace.py walks the small shapes)."""
+    _, words = p.read_workspace()
+    nz = np.flatnonzero(words)
+    assert len(nz) == 0, f"{tag}: workspace word {int(nz[0])} of {len(words)} is {int(words[nz[0]]):#x} behind {p.profile_kernel()} ({len(nz)} words are not zero)"
+
+
 # ---- golden fixtures (reference outputs) ------------------------------------------------------------------
 def test_the_library_on_this_box_was_built_from_these_sources():
     """The driver's box runs a PREBUILT libsjgpu.so (it travels with the snapshot): its stamp -- the sha256 of the sources it was compiled from,
@@ -303,6 +311,8 @@ def test_two_contexts_on_two_threads(orc):
                 if (err, n) != want[i][:2] or not np.array_equal(p.structural_indexes[: n + 3], want[i][2]):
                     errors.append((i, err, n))
                     break
+            assert_workspace_clean(p, f"thread {i}")  # (AUTO: 400 000 bytes take the 16 KiB-tile single-pass kernel)
+            assert p.gave_up_count() == 0, p.gave_up_count()
             p.close()
         except Exception as e:  # noqa: BLE001
             errors.append((i, repr(e)))
@@ -429,10 +439,13 @@ def test_pipelined_kernels_are_deterministic(orc):
         n, flags, _ = p.result(stream)
         assert (n, flags) == (on, 0), (rep, n, on, flags)
         assert orc.fnv(idx[: n + 3].cpu().numpy().view(np.uint32)) == want_idx, rep
+        assert_workspace_clean(p, f"stage 1, repetition {rep}")  # (more tiles than workgroups: the only place where a workgroup loops over many tiles)
         assert p.minify_device(buf.data_ptr(), L, dst.data_ptr(), stream) == 0
         _, mflags, mlen = p.result(stream)
         assert (mlen, mflags) == (L, 0), (rep, mlen, L, mflags)  # minified text is its own minification
         assert bool((dst[:L] == buf).all()), rep
+        assert_workspace_clean(p, f"minify, repetition {rep}")
+    assert p.gave_up_count() == 0, p.gave_up_count()
     p.close()
 
 
@@ -1251,6 +1264,8 @@ def test_full_size_device_resident(orc, kind, pipeline):
         assert p.validate_utf8_device(buf.data_ptr(), L, stream) == 0
         assert p.result(stream)[1] & capi.F_UTF8_ERROR, pos
         buf[pos] = old
+    assert_workspace_clean(p, f"{kind} {pipeline}")
+    assert p.gave_up_count() == 0, p.gave_up_count()
     p.close()
 
 

@@ -85,6 +85,26 @@ def test_the_guards_catch_a_tail_that_leaves_as_a_whole_vector(tmp_path):
     assert any(f"MISMATCH {road}: " in err for road in ("split stage 1", "fused stage 1 (16 KiB tiles)", "pipelined stage 1", "direct stage 1")), err[-3000:]
 
 
+@pytest.mark.parametrize("word,roads,spared", [
+    (1, ("on-chip minify",), ("fused stage 1 (16 KiB tiles)", "pipelined stage 1", "fused minify (16 KiB tiles)")),
+    (2, ("fused stage 1 (16 KiB tiles)", "pipelined stage 1", "fused minify (16 KiB tiles)", "on-chip minify"), ())])
+def test_the_look_at_the_workspace_sees_one_word_left_behind(tmp_path, word, roads, spared):
+    """The single-pass kernels clear nothing in front of themselves: each trusts that the one before it left [descriptors][control words] all zero
+    (sjgpu_fused.hip: leave_and_clean), and check_workspace_clean in the driver looks at every word behind every launch.  That look has teeth: with
+    SJGPU_SELFTEST_LEAVE_DIRTY=1 the last workgroup skips the second ticket counter -- sixteen words behind the first, drawn from by k_minify_onchip
+    alone -- and the minify road must fail with the workspace message while the roads that never touch that word stay clean; with =2 it skips the
+    [ticket, done] word and every road must fail.  (The GPU tier looks at the same words on the device: tests/test_gpu_workspace.py.)"""
+    import re
+    exe = _build(tmp_path, ("-DSJGPU_SELFTEST_LEAVE_DIRTY=%d" % word,))
+    p = subprocess.run([exe, "1", "40", "200", "all"], capture_output=True, timeout=1800, env=dict(os.environ, SJ_EMU_MAX_FAILURES="100000"))
+    err = p.stderr.decode()
+    assert p.returncode != 0, p.stdout.decode()[-500:]
+    for road in roads:
+        assert re.search(r"MISMATCH %s: len \d+: workspace word \d+ is [0-9a-f]+ behind the kernel" % re.escape(road), err), (road, err[-3000:])
+    for road in spared:
+        assert "MISMATCH %s: " % road not in err, (road, err[-3000:])
+
+
 @pytest.mark.parametrize("waves", ["4", "16"])
 def test_the_other_workgroup_shapes_of_the_single_pass_kernels(emu, waves):
     """The single-pass kernels run with eight waves per workgroup since round 4 (128 KiB / 64 KiB tiles: half the tickets and look-backs per byte); the
