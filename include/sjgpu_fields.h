@@ -35,7 +35,9 @@ extern "C" {
  * characters) and of sjgpu_cast_cells_device; value_dev / tag_dev[0 .. *fields_out) is a row of cells, a valid input of every *_from_cells call (this one
  * included: a second nesting level is one more call) and of the cast.
  * field_cap too small: SJGPU_E_OVERFLOW, *fields_out says what is needed, offsets_dev and status_dev are complete and nothing is written to the four cell
- * arrays.  A total beyond 32 bits: CAPACITY (1).  rows == 0: 0 with offsets_dev[0] = 0.  docs == 0 is served: no container root has a document.
+ * arrays.  A total beyond 32 bits: CAPACITY (1) -- the total out-parameter holds
+ * the 64-bit total, status and counts are complete, offsets_dev is written but meaningless (its 32-bit words wrapped) and nothing is written to the data arrays.
+ * rows == 0: 0 with offsets_dev[0] = 0.  docs == 0 is served: no container root has a document.
  * SJGPU_E_BADARG, before anything is read or enqueued: a null pointer (status_dev may be null when rows is 0, the four cell arrays when field_cap is 0),
  * tape_dev, root_value_dev, key_value_dev or value_dev not 8-byte, docs_dev not 16-byte, offsets_dev not 4-byte aligned (status_dev, the tag rows and
  * root_tag_dev begin at any byte), tape_words or string_bytes beyond 32 bits, docs or rows + 1 beyond 0xFFFFFFF0; and a table whose tape_begin /

@@ -39,7 +39,9 @@ extern "C" {
  *   chars_dev                the texts back to back, no terminators
  * The pair is Arrow's utf8 layout, and what the consumers of sjgpu_gather_strings_device's offsets / chars take.
  * chars_cap too small: SJGPU_E_OVERFLOW, *bytes_out says what is needed, offsets_dev and status_dev are complete and nothing is written to chars_dev; chars_cap == 0
- * with a null chars_dev is how to ask.  A total beyond 32 bits: CAPACITY (1).  rows == 0: 0 with offsets_dev[0] = 0.  docs == 0 is served: no container root has a document.
+ * with a null chars_dev is how to ask.  A total beyond 32 bits: CAPACITY (1) -- the total out-parameter holds
+ * the 64-bit total, status and counts are complete, offsets_dev is written but meaningless (its 32-bit words wrapped) and nothing is written to the data arrays.
+ * rows == 0: 0 with offsets_dev[0] = 0.  docs == 0 is served: no container root has a document.
  * SJGPU_E_BADARG, before anything is read or enqueued: a null pointer (status_dev may be null when rows is 0, chars_dev when chars_cap is 0), tape_dev or
  * root_value_dev not 8-byte, docs_dev not 16-byte, offsets_dev not 4-byte aligned (status_dev, chars_dev and root_tag_dev begin at any byte), tape_words or
  * string_bytes beyond 32 bits, docs or rows + 1 beyond 0xFFFFFFF0; and a table whose tape_begin / string_begin run backwards or end beyond tape_words / string_bytes.

@@ -42,7 +42,9 @@ extern "C" {
  * Composition: value_dev / tag_dev[0 .. *matches_out) is ONE flattened pair of rows in the cell encoding: a valid input of this call
  * (a third nesting level is one more call), of sjgpu_at_pointers_from_cells_device and of sjgpu_gather_strings_device.
  * match_cap too small: SJGPU_E_OVERFLOW, *matches_out says what is needed, offsets_dev and status_dev are complete and nothing is
- * written to value_dev or tag_dev.  A total beyond 32 bits: CAPACITY (1).  K == 0 or rows == 0: 0 with offsets_dev[0] = 0.  docs == 0
+ * written to value_dev or tag_dev.  A total beyond 32 bits: CAPACITY (1) -- the total out-parameter holds
+ * the 64-bit total, status and counts are complete, offsets_dev is written but meaningless (its 32-bit words wrapped) and nothing is written to the data arrays.
+ * K == 0 or rows == 0: 0 with offsets_dev[0] = 0.  docs == 0
  * is served: no container root has a document.  SJGPU_E_BADARG: a null pointer (value_dev and tag_dev may be null when match_cap is 0),
  * tape_dev, root_value_dev or value_dev not 8-byte, docs_dev not 16-byte, offsets_dev not 4-byte aligned (status_dev, tag_dev and
  * root_tag_dev begin at any byte), K or a path beyond the limits, K * rows + 1 beyond 0xFFFFFFF0 -- refused before anything is read

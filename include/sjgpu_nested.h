@@ -54,7 +54,8 @@ typedef struct sjgpu_write_field {        /* HOST memory, K of them */
  *                        as null.  (A row with status 19 counts nowhere else.)
  * n == 0: 0 with offsets_dev[0] = 0 and six zero counts.
  * Capacity, word for word the plain writer's: chars_cap too small: SJGPU_E_OVERFLOW, *bytes_out says what is needed, offsets_dev, status_dev and counts_dev are complete
- * and nothing is written to chars_dev; chars_cap == 0 with a null chars_dev is how to ask.  A total beyond 32 bits: CAPACITY (1).
+ * and nothing is written to chars_dev; chars_cap == 0 with a null chars_dev is how to ask.  A total beyond 32 bits: CAPACITY (1) -- the total out-parameter holds
+ * the 64-bit total, status and counts are complete, offsets_dev is written but meaningless (its 32-bit words wrapped) and nothing is written to the data arrays.
  * SJGPU_E_BADARG, before anything is read or enqueued: everything sjgpu_write_records_device refuses, applied per field (a null `fields` when K > 0; the key limits
  * only where keys are written); a flag outside the four; ARRAY_ROWS with OMIT_NULLS; ARRAY_ROWS with BARE; BARE with K != 1; a list field whose element kind is
  * outside 1-5, 8, 9; list_offsets_dev not 4-byte, list_valid_dev not 8-byte aligned; elements + 1 beyond 0xFFFFFFF0; for a list field, when n > 0 and

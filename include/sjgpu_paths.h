@@ -44,7 +44,8 @@ extern "C" {
  * value_dev and tag_dev are ONE flattened pair of rows: a valid input of sjgpu_gather_strings_device with docs = *matches_out, whose
  * offsets then give one string slice per match.
  * match_cap (the matches value_dev and tag_dev have room for) too small: SJGPU_E_OVERFLOW, *matches_out says what is needed,
- * offsets_dev and status_dev are complete and nothing is written to value_dev or tag_dev.  A total beyond 32 bits: CAPACITY (1).
+ * offsets_dev and status_dev are complete and nothing is written to value_dev or tag_dev.  A total beyond 32 bits: CAPACITY (1) -- the total out-parameter holds
+ * the 64-bit total, status and counts are complete, offsets_dev is written but meaningless (its 32-bit words wrapped) and nothing is written to the data arrays.
  * K == 0 or docs == 0: 0 with offsets_dev[0] = 0.  Nothing is written outside offsets_dev[0 .. K * docs], status_dev[0 .. K * docs),
  * value_dev / tag_dev[0 .. *matches_out): the fill never writes at or beyond offsets[c + 1], whatever the tape says.  Nothing is read
  * outside the arrays and the table: a tape word that points elsewhere ends its level instead of being followed.
@@ -66,7 +67,7 @@ int sjgpu_at_paths_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_wo
 
 /* ---- the same column, breadth first (the k_wide_* kernels in sjgpu_query.hip) ------------------------------------------------------
  * The contract of sjgpu_at_paths_device, word for word: the cells, the level program and its limits, the alignments and refusals, K == 0 /
- * docs == 0, CAPACITY for a total beyond 32 bits, SJGPU_E_OVERFLOW with offsets_dev and status_dev complete, *matches_out set and nothing
+ * docs == 0, CAPACITY for a total beyond 32 bits and what it leaves behind, SJGPU_E_OVERFLOW with offsets_dev and status_dev complete, *matches_out set and nothing
  * written to value_dev / tag_dev, nothing written outside the contracted ranges, nothing read outside the three arrays, and the call
  * waits for the stream.  Over tapes that sjgpu_stage2_device / sjgpu_stage2_many_device delivered all four outputs are bit for bit those
  * of sjgpu_at_paths_device.  Over words that are no tape the results are unspecified; the call still ends, stays inside its arrays and

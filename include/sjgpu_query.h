@@ -63,7 +63,9 @@ int sjgpu_at_pointers_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape
  *   offsets_dev[0 .. docs]  u32, the exclusive sum of the lengths; offsets_dev[docs] == *bytes_out
  *   chars_dev               the characters back to back; neither the records' length words nor their terminators
  * chars_cap too small: SJGPU_E_OVERFLOW, *bytes_out says what is needed, the offsets are complete and nothing is written to chars_dev.
- * A total beyond 32 bits: CAPACITY (1).  docs == 0: 0 with offsets_dev[0] = 0.  offsets_dev 4-byte, value_row_dev 8-byte aligned
+ * A total beyond 32 bits: CAPACITY (1) -- the total out-parameter holds
+ * the 64-bit total, status and counts are complete, offsets_dev is written but meaningless (its 32-bit words wrapped) and nothing is written to the data arrays.
+ * docs == 0: 0 with offsets_dev[0] = 0.  offsets_dev 4-byte, value_row_dev 8-byte aligned
  * (SJGPU_E_BADARG otherwise); chars_dev and tag_row_dev begin at any byte.  The copy is chunk-parallel (16 bytes of the OUTPUT per lane,
  * its cell found by a search in the offsets): one long string among short ones is shared by as many lanes as it has chunks.
  * Waits for the stream: the total is read back. */

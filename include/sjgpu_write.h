@@ -50,7 +50,8 @@ typedef struct sjgpu_write_column {          /* HOST memory, K of them */
  *                         that are not finite.  (The cells of a row with status 19 count nowhere: nothing was written for them.)
  * K == 0: {} per row.  n == 0: 0 with offsets_dev[0] = 0 and four zero counts.
  * chars_cap too small: SJGPU_E_OVERFLOW, *bytes_out says what is needed, offsets_dev, status_dev and counts_dev are complete and nothing is written to chars_dev;
- * chars_cap == 0 with a null chars_dev is how to ask.  A total beyond 32 bits: CAPACITY (1).
+ * chars_cap == 0 with a null chars_dev is how to ask.  A total beyond 32 bits: CAPACITY (1) -- the total out-parameter holds
+ * the 64-bit total, status and counts are complete, offsets_dev is written but meaningless (its 32-bit words wrapped) and nothing is written to the data arrays.
  * SJGPU_E_BADARG, before anything is read or enqueued: a null ctx, offsets_dev, counts_dev or bytes_out, a null status_dev when n > 0, a null chars_dev when
  * chars_cap > 0, a null columns when K > 0, a null key with key_len > 0; when n > 0, a null values_dev (kinds 1-4, 9), offsets_dev (5, 8) or chars_dev (5, 8, 9 with
  * chars_bytes > 0) of a column; a kind or a flag outside the lists; K > 64; key_len > 1024; escaped "key": prefixes that together exceed 8 192 bytes; values_dev,

@@ -361,8 +361,11 @@ def _to_capacity(call, cap):
 
 
 def _refused(name, rc):
+    """raises for a call that did not end with 0; the error carries the call's answer as .code (CAPACITY: a total beyond 32 bits, which no larger array cures)"""
     if rc:
-        raise SjgpuError(f"{name} refused its arguments ({rc})")
+        err = SjgpuError(f"{name}: the output needs offsets beyond 32 bits (CAPACITY)" if rc == CAPACITY else f"{name} refused its arguments ({rc})")
+        err.code = rc
+        raise err
 
 
 class ResidentStream:

@@ -240,8 +240,13 @@ constexpr u32 RES_THREADS = 1024, RES_WAVES = RES_THREADS / 64, RES_MAX_TILES = 
 // ~200 instructions on one CU are 3 000 cycles per tile.  Now a tile computes, from its own summaries, its totals for BOTH states it may start in, publishes
 // them -- two 64-bit words in the padding of its first two summaries (k_strs_count has zeroed them; the top bit says "written": the data is the flag, as
 // in sjgpu_fused.hip) -- and reads the words of the tiles in front of it (one thread each; workgroups are dispatched in order, so those run or have
-// run); a walk over at most 255 pairs of totals gives the tile its state and its bases.  A tile holds at most 1024 x 2.5 x 16 KiB = 40 MiB (26 bits)
-// and 8 M opening quotes (23 bits).
+// run); a walk over at most 255 pairs of totals gives the tile its state and its bases.  A tile holds at most 1024 x 2.5 x 16 KiB = 40 MiB (26 bits:
+// below 2^26) and 1024 x 8192 = 2^23 opening quotes EXACTLY when it is nothing but `""` -- a count that needs 24 bits, not 23.
+constexpr u32 TILE_BYTE_BITS = 26, TILE_OPEN_BITS = 24;
+constexpr u64 TILE_BYTE_MASK = (u64(1) << TILE_BYTE_BITS) - 1, TILE_OPEN_MASK = (u64(1) << TILE_OPEN_BITS) - 1;
+static_assert(u64(RES_THREADS) * SEG_BYTES / 2 <= TILE_OPEN_MASK, "word b: a tile of nothing but empty strings has RES_THREADS * SEG_BYTES / 2 opening quotes");
+static_assert(u64(RES_THREADS) * SEG_BYTES * 5 / 2 <= TILE_BYTE_MASK, "word a: a tile's bytes for either state");
+static_assert(2 * TILE_BYTE_BITS + 3 < 63 && 2 * TILE_OPEN_BITS < 63, "the fields lie below the written flag");
 __device__ __forceinline__ u64 *tile_word(strs_summary *summ, u32 tile, u32 which) { return reinterpret_cast<u64 *>(&summ[u64(tile) * RES_THREADS + which].pad[1]); }
 static_assert(sizeof(strs_summary) == 32 && offsetof(strs_summary, pad) == 20, "tile_word: an aligned 64-bit word inside the padding");
 constexpr u64 TILE_WRITTEN = u64(1) << 63;
@@ -293,8 +298,8 @@ __global__ __launch_bounds__(RES_THREADS) void k_strs_resolve(strs_summary *__re
   if (t == 0) { // the tile's own words first: nobody behind it waits for what it is about to wait for
     for (u32 w = 0; w < RES_WAVES; w++) { tot0 += sh_tot[0][w]; tot1 += sh_tot[1][w]; tile_bad |= sh_bad[w]; }
     if (tile + 1 < ntiles) { // (a tile with a tile behind it is full: its second summary exists)
-      const u64 a = (tot0 & 0x3FFFFFFull) | ((tot1 & 0x3FFFFFFull) << 26) | (u64(par_total & 1u) << 52) | (u64(tile_bad) << 53) | TILE_WRITTEN;
-      const u64 b = (tot0 >> 32) | ((tot1 >> 32) << 23) | TILE_WRITTEN;
+      const u64 a = (tot0 & TILE_BYTE_MASK) | ((tot1 & TILE_BYTE_MASK) << TILE_BYTE_BITS) | (u64(par_total & 1u) << 52) | (u64(tile_bad) << 53) | TILE_WRITTEN;
+      const u64 b = (tot0 >> 32) | ((tot1 >> 32) << TILE_OPEN_BITS) | TILE_WRITTEN;
       __hip_atomic_store(tile_word(summ, tile, 0), a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(tile_word(summ, tile, 1), b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -312,8 +317,8 @@ __global__ __launch_bounds__(RES_THREADS) void k_strs_resolve(strs_summary *__re
     u64 bytes = 0;
     for (u32 w = 0; w < tile; w++) {
       const u64 a = sh_back[0][w], b = sh_back[1][w];
-      bytes += s ? (a >> 26) & 0x3FFFFFFull : a & 0x3FFFFFFull;
-      opens += u32(s ? (b >> 23) & 0x7FFFFFull : b & 0x7FFFFFull);
+      bytes += s ? (a >> TILE_BYTE_BITS) & TILE_BYTE_MASK : a & TILE_BYTE_MASK;
+      opens += u32(s ? (b >> TILE_OPEN_BITS) & TILE_OPEN_MASK : b & TILE_OPEN_MASK);
       bad |= u32(a >> (53u + s)) & 1u;
       s ^= u32(a >> 52) & 1u;
     }

@@ -844,6 +844,43 @@ def test_string_stream_takes_valid_documents_and_only_those(orc, monkeypatch):
     p.close()
 
 
+@pytest.mark.parametrize("lead", [b"", b" "], ids=["tile 0 is nothing but pairs", "one blank in front"])
+def test_string_stream_with_a_tile_full_of_opening_quotes(orc, lead):
+    """k_strs_resolve publishes a tile's opening quotes, for either state the tile may start in, in two fields of one 64-bit word.  A tile is 1024 segments of
+    16 KiB; made of nothing but `""` it holds 1024 x 8192 = 2^23 opening quotes exactly, one more than 23 bits hold: packed in 23 bits the count read back as 0,
+    ctrl->opens came out 2^23 short of the listed strings and the document -- every string of it valid and listed -- took the per-string road (right bytes, wrong
+    road).  2^23 + 1024 pairs and no bracket in front: tile 0 is full, begins outside a string and has a tile behind it, so it publishes; with one blank in front it
+    holds 2^23 - 1 whole pairs and the opening quote of the next, whose closing quote is tile 1's first byte.  The buffer is 5 bytes per 2 of input, more than any
+    JSON document needs (sjgpu.h sizes the buffer for 5 per 3): the capacity here is the oracle's byte count.  The CPU tier has no emulation of k_strs_resolve
+    (tests/host/test_string_stream.cpp runs the block functions only), so this packing is checked on the device alone."""
+    import torch
+    pairs = (1 << 23) + 1024
+    a = np.frombuffer(lead + b'""' * pairs, np.uint8)
+    assert len(a) > 1024 * 16384  # a tile behind tile 0
+    e1, n, oidx = orc.stage1(a, 0)
+    assert (e1, n) == (0, pairs)  # stage 1 lists every opening quote
+    oerr, want, ooff, ostrings, obad = orc.string_buffer(a, oidx[:n], n)
+    assert (oerr, ostrings, obad, len(want)) == (0, pairs, checkers.NO_STRING, 5 * pairs)
+    p = capi.DomParserImplementation(32 << 20)
+    stream = torch.cuda.current_stream().cuda_stream
+    L = len(a)
+    buf = torch.from_numpy(a.copy()).cuda()
+    idx = torch.empty(L + 16, dtype=torch.int32, device="cuda")
+    assert p.stage1_device(buf.data_ptr(), L, idx.data_ptr(), L + 3, stream) == 0
+    assert p.result(stream)[:2] == (n, 0)
+    cap = len(want)
+    out = torch.full((cap + 4096,), 0xEE, dtype=torch.uint8, device="cuda")
+    off = torch.full((n + 1,), -1, dtype=torch.int32, device="cuda")
+    err, used, strings, bad = p.parse_strings_device(buf.data_ptr(), L, idx.data_ptr(), n, out.data_ptr(), cap, off.data_ptr(), False, stream)
+    assert (err, used, strings, bad) == (0, len(want), pairs, checkers.NO_STRING), (err, used, strings, bad)
+    assert bool((out[used:] == 0xEE).all()), "a byte behind the last record was written"
+    assert torch.equal(out[:used], torch.from_numpy(want).cuda()), "the string buffer is not the oracle's"
+    assert torch.equal(off, torch.arange(0, 5 * (n + 1), 5, dtype=torch.int32, device="cuda")), "the offsets: record i begins at 5 i"
+    assert np.array_equal(ooff, np.arange(0, 5 * n, 5, dtype=np.uint32))  # (the oracle's own offsets are that progression)
+    assert p.string_path() == 1, "every string is valid and listed: the stream's road"
+    p.close()
+
+
 def test_string_stream_random_documents(orc):
     """random valid documents and token-level mutations of them, several thousand in one NDJSON-like buffer each way"""
     import jsongen
