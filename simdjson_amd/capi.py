@@ -93,6 +93,9 @@ SJGPU_E_INTERNAL = -7  # (include/sjgpu_dict.h) a bounded loop of the library ra
 # what include/sjgpu_json.h declares (cells as JSON text: minify(element) per cell into offsets + chars); the bindings are the free functions of
 # simdjson_amd/json_text.py
 JSON_EXPORTS = ["sjgpu_serialize_cells_device"]
+# what include/sjgpu_json_wide.h declares (the same texts, one lane per tape word); the bindings are the free functions of simdjson_amd/json_text_wide.py
+JSON_WIDE_EXPORTS = ["sjgpu_serialize_cells_wide_device"]
+SJGPU_E_RANGE = -8  # (include/sjgpu_json_wide.h) the range space of the call exceeds 0xFFFFFFF0 slots
 
 
 # what include/sjgpu_write.h declares (typed columns as JSON records: one object per row into offsets + chars); the bindings are the free functions of
@@ -269,6 +272,8 @@ def load_library():
     L.sjgpu_cell_kinds_by_code_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     L.sjgpu_serialize_cells_device.restype = ctypes.c_int
     L.sjgpu_serialize_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, u64p]
+    L.sjgpu_serialize_cells_wide_device.restype = ctypes.c_int
+    L.sjgpu_serialize_cells_wide_device.argtypes = L.sjgpu_serialize_cells_device.argtypes
     L.sjgpu_write_records_device.restype = ctypes.c_int
     L.sjgpu_write_records_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, u64p]
     L.sjgpu_write_nested_device.restype = ctypes.c_int

@@ -10,6 +10,7 @@
 #include "sjgpu_fields.h"
 #include "sjgpu_dict.h"
 #include "sjgpu_json.h"
+#include "sjgpu_json_wide.h"
 #include "sjgpu_write.h"
 #include "sj_path_program.h"
 #include "sj_write_table.h"
@@ -769,6 +770,71 @@ int sjgpu_serialize_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t 
     launch_json_fill(tape, sbuf, string_bytes, table, root_value, root_tag, rows, where, offsets, static_cast<uint8_t *>(chars_dev), ctx->d_tmp, s);
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s)); // (the verdicts and the workspace are free again when the call returns)
+  }
+  return 0;
+}
+
+// ---- cells as JSON text, breadth first (sjgpu_json_wide.hip; include/sjgpu_json_wide.h) ------------------------------------------------------------------------
+// The narrow call's refusals, prologue and decisions, word for word.  Two waits in front of the fill: the size of the range space sizes the workspace (and is what
+// SJGPU_E_RANGE refuses), the total decides the fill.  The roots' block lies behind the context's query block, the slots' in d_tmp
+int sjgpu_serialize_cells_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                                      uint32_t docs, const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev,
+                                      uint64_t chars_cap, void *stream, uint64_t *bytes_out) {
+  if (bytes_out) { *bytes_out = 0; }
+  if (!string_buf_dev || !offsets_dev || !bytes_out || (rows && !status_dev) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
+  if (reinterpret_cast<uintptr_t>(offsets_dev) & 3u) { return SJGPU_E_BADARG; }
+  hipStream_t s = nullptr;
+  bool done = true;
+  int rc = fields_begin(ctx, tape_dev, tape_words, string_bytes, docs_dev, docs, root_value_dev, root_tag_dev, rows, 0, stream, &s, &done);
+  if (done) { return rc; }
+  if (rows == 0) {
+    SJ_TRY(ctx, hipMemsetAsync(offsets_dev, 0, sizeof(uint32_t), s));
+    SJ_TRY(ctx, hipStreamSynchronize(s));
+    return 0;
+  }
+  uint32_t *offsets = static_cast<uint32_t *>(offsets_dev);
+  const doc_span_dev *table = static_cast<const doc_span_dev *>(docs_dev);
+  const uint64_t *tape = static_cast<const uint64_t *>(tape_dev);
+  const uint8_t *sbuf = static_cast<const uint8_t *>(string_buf_dev);
+  const uint64_t *root_value = static_cast<const uint64_t *>(root_value_dev);
+  const uint8_t *root_tag = static_cast<const uint8_t *>(root_tag_dev);
+  uint8_t *status = static_cast<uint8_t *>(status_dev);
+  // (the table check is over and the stream drained: the query block may move)
+  rc = grow(ctx, reinterpret_cast<void **>(&ctx->d_query), &ctx->d_query_bytes, 256 + json_wide_root_bytes(rows));
+  if (rc) { return rc; }
+  void *root_space = ctx->d_query + 256;
+  uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
+  const count_total_dev *range_dev = launch_json_wide_extents(tape, table, docs, root_value, root_tag, rows, root_space, s);
+  SJ_TRY(ctx, hipGetLastError());
+  SJ_TRY(ctx, hipMemcpyAsync(total, &range_dev->total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  const uint64_t range_words = *total;
+  if (range_words > 0xFFFFFFF0ull) {
+    // the statuses alone, by the narrow count, its offsets into the workspace: nothing else of the caller's is written
+    const size_t narrow = (json_workspace_bytes(rows) + 255) & ~size_t(255);
+    rc = ensure_tmp(ctx, narrow + (size_t(rows) + 1) * sizeof(uint32_t));
+    if (rc) { return rc; }
+    (void)launch_json_count(tape, sbuf, string_bytes, table, docs, root_value, root_tag, rows, json_wide_where(root_space, rows),
+                            reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->d_tmp) + narrow), status, ctx->d_tmp, s);
+    SJ_TRY(ctx, hipGetLastError());
+    SJ_TRY(ctx, hipStreamSynchronize(s));
+    return SJGPU_E_RANGE;
+  }
+  rc = ensure_tmp(ctx, json_wide_word_bytes(rows, range_words));
+  if (rc) { return rc; }
+  const count_total_dev *total_dev = nullptr;
+  SJ_TRY(ctx, launch_json_wide_count(tape, sbuf, string_bytes, table, root_value, root_tag, rows, range_words, offsets, status, root_space, ctx->d_tmp, s, &total_dev));
+  SJ_TRY(ctx, hipGetLastError());
+  SJ_TRY(ctx, hipMemcpyAsync(total, &total_dev->total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  SJ_TRY(ctx, hipStreamSynchronize(s));
+  const uint64_t bytes = *total;
+  *bytes_out = bytes;
+  if (bytes > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
+  if (bytes > chars_cap) { return SJGPU_E_OVERFLOW; }
+  if (bytes) {
+    launch_json_wide_fill(tape, sbuf, string_bytes, table, root_value, root_tag, rows, range_words, static_cast<uint8_t *>(chars_dev), root_space, ctx->d_tmp, s);
+    SJ_TRY(ctx, hipGetLastError());
+    SJ_TRY(ctx, hipStreamSynchronize(s)); // (the roots' block and the workspace are free again when the call returns)
   }
   return 0;
 }

@@ -420,6 +420,24 @@ const count_total_dev *launch_json_count(const uint64_t *tape, const uint8_t *st
                                          const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s);
 void launch_json_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
                       uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s);
+// ---- cells as JSON text, breadth first (sjgpu_json_wide.hip: sjgpu_serialize_cells_wide_device, include/sjgpu_json_wide.h) -------------------------------------
+// rows >= 1, docs >= 0; a table that passed the check.  Two blocks of device memory, both 256-byte aligned: root_space, json_wide_root_bytes(rows), which holds the
+// verdicts of k_rows_locate (json_wide_where), the roots' first slots and their flags; word_space, json_wide_word_bytes(rows, R), asked for once R is known.
+// launch_json_wide_extents: locate, the extents and their scan -> where R, the size of the range space, lies in 64 bits (->total).  R <= 0xFFFFFFF0 is the caller's to
+// check.  launch_json_wide_count: status[r] and offsets[0 .. rows], -> *total: where the 64-bit total of the texts lies; -> what the memsets returned.
+// launch_json_wide_fill, when the total fits: the bytes of cell r to chars[offsets[r] .. offsets[r + 1]), never beyond.  json_wide_share: the slots of one workgroup
+// (a wave's share is 64 of them, a lane's 1), for the tests that stand on their edges
+size_t json_wide_root_bytes(uint32_t rows);
+size_t json_wide_word_bytes(uint32_t rows, uint64_t range_words);
+uint32_t *json_wide_where(void *root_space, uint32_t rows);
+uint32_t json_wide_share();
+const count_total_dev *launch_json_wide_extents(const uint64_t *tape, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value, const uint8_t *root_tag, uint32_t rows,
+                                                void *root_space, hipStream_t s);
+hipError_t launch_json_wide_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value,
+                                  const uint8_t *root_tag, uint32_t rows, uint64_t range_words, uint32_t *offsets, uint8_t *status, void *root_space, void *word_space,
+                                  hipStream_t s, const count_total_dev **total);
+void launch_json_wide_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                           uint32_t rows, uint64_t range_words, uint8_t *chars, void *root_space, void *word_space, hipStream_t s);
 // ---- typed columns as JSON records (sjgpu_write.hip: sjgpu_write_records_device, include/sjgpu_write.h) -----------------------------------------------------
 // One column as the kernels read it, K of them in device memory (sj_write_table.h makes them from the caller's sjgpu_write_column and escapes the keys):
 // key_at / key_len: the column's escaped "key": prefix inside the `keys` bytes.

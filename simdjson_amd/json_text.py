@@ -21,11 +21,12 @@ def serialize_cells_device(p, tape_ptr, tape_words, strbuf_ptr, strbuf_bytes, do
     return p._raise_infra("sjgpu_serialize_cells_device", rc), int(total.value)
 
 
-def _serialize(p, S, roots, offsets, status, cap):
-    """one sjgpu_serialize_cells_device over the tapes of S, into characters it allocates for cap bytes: the `call` of _to_capacity -> (rc, bytes, chars)"""
+def _serialize(p, S, roots, offsets, status, cap, entry=None):
+    """one sjgpu_serialize_cells_device (entry: the binding of another call with its contract, simdjson_amd/json_text_wide.py) over the tapes of S, into characters it
+    allocates for cap bytes: the `call` of _to_capacity -> (rc, bytes, chars)"""
     import torch
     chars = torch.empty(max(cap, 1), dtype=torch.uint8, device=S.dev)
-    rc, total = serialize_cells_device(p, *S.args(), *roots, offsets.data_ptr(), status.data_ptr(), chars.data_ptr(), cap, S.stream)
+    rc, total = (entry or serialize_cells_device)(p, *S.args(), *roots, offsets.data_ptr(), status.data_ptr(), chars.data_ptr(), cap, S.stream)
     return rc, total, chars
 
 
@@ -35,6 +36,11 @@ def json_column_many(p, data, path, wide=False, max_depth=1024):
     repeated once with the capacity it reported; the first guess is the source's length, which a minified text of it rarely exceeds (a \\u0001 is six bytes either
     way, an é written as \\u00e9 shrinks; a number may grow: 1e2 becomes 100.0) --, with everything resident.  Text r is chars[offsets[r] .. offsets[r + 1]).
     -> (offsets uint32[rows + 1], chars uint8[bytes], status uint8[rows]); raises SjgpuError when no document was delivered"""
+    return _json_column(p, data, path, wide, max_depth, None, "sjgpu_serialize_cells_device")
+
+
+def _json_column(p, data, path, wide, max_depth, entry, name):
+    """json_column_many with the serialising call given (entry: None for sjgpu_serialize_cells_device; name: what a refusal is reported as)"""
     from .capi import SjgpuError
     import torch
     S = ResidentStream(p, data, max_depth)
@@ -44,8 +50,8 @@ def json_column_many(p, data, path, wide=False, max_depth=1024):
     offsets = torch.empty(rows + 1, dtype=torch.int32, device=S.dev)
     status = torch.empty(max(rows, 1), dtype=torch.uint8, device=S.dev)
     roots = (root_values.data_ptr(), root_tags.data_ptr(), rows)
-    rc, total, chars = _to_capacity(lambda cap: _serialize(p, S, roots, offsets, status, cap), int(S.length))
-    _refused("sjgpu_serialize_cells_device", rc)
+    rc, total, chars = _to_capacity(lambda cap: _serialize(p, S, roots, offsets, status, cap, entry), int(S.length))
+    _refused(name, rc)
     S.synchronize()
     return offsets.cpu().numpy().view(np.uint32), chars[:total].cpu().numpy(), status[:rows].cpu().numpy()
 
@@ -54,6 +60,11 @@ def documents_as_json_many(p, data, max_depth=1024):
     """Every document of a stream as its minified text, through its tape, one row per document: json_column_many with the documents' root cells --
     sjgpu_at_pointers_device with the empty pointer (a bare `$` is no path: at_path_with_wildcard answers it with INVALID_JSON_POINTER) -- in the place of a path's matches.
     -> (offsets uint32[docs + 1], chars uint8[bytes], status uint8[docs]); raises SjgpuError when no document was delivered"""
+    return _documents_as_json(p, data, max_depth, None, "sjgpu_serialize_cells_device")
+
+
+def _documents_as_json(p, data, max_depth, entry, name):
+    """documents_as_json_many with the serialising call given, as _json_column"""
     from .capi import SjgpuError
     import torch
     S = ResidentStream(p, data, max_depth)
@@ -65,7 +76,7 @@ def documents_as_json_many(p, data, max_depth=1024):
     offsets = torch.empty(S.docs + 1, dtype=torch.int32, device=S.dev)
     status = torch.empty(S.docs, dtype=torch.uint8, device=S.dev)
     roots = (root_values.data_ptr(), root_tags.data_ptr(), S.docs)
-    rc, total, chars = _to_capacity(lambda cap: _serialize(p, S, roots, offsets, status, cap), int(S.length))
-    _refused("sjgpu_serialize_cells_device", rc)
+    rc, total, chars = _to_capacity(lambda cap: _serialize(p, S, roots, offsets, status, cap, entry), int(S.length))
+    _refused(name, rc)
     S.synchronize()
     return offsets.cpu().numpy().view(np.uint32), chars[:total].cpu().numpy(), status.cpu().numpy()
