@@ -64,7 +64,7 @@ def sjgpu_source_stamp():
     for f in [*_csrc(*SJGPU_SOURCES), *_csrc(*SJGPU_HEADERS), os.path.join(_paths.INCLUDE_DIR, "sjgpu.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_stream.h"),
               os.path.join(_paths.INCLUDE_DIR, "sjgpu_query.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_paths.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_rows.h"),
               os.path.join(_paths.INCLUDE_DIR, "sjgpu_lists.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_cast.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_fields.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_dict.h"),
-              os.path.join(_paths.INCLUDE_DIR, "sjgpu_json.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_json_wide.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_write.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_nested.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_debug.h")]:
+              os.path.join(_paths.INCLUDE_DIR, "sjgpu_json.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_json_wide.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_pretty.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_write.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_nested.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_debug.h")]:
         h.update(os.path.relpath(f, _paths.REPO_ROOT).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()

@@ -96,6 +96,8 @@ JSON_EXPORTS = ["sjgpu_serialize_cells_device"]
 # what include/sjgpu_json_wide.h declares (the same texts, one lane per tape word); the bindings are the free functions of simdjson_amd/json_text_wide.py
 JSON_WIDE_EXPORTS = ["sjgpu_serialize_cells_wide_device"]
 SJGPU_E_RANGE = -8  # (include/sjgpu_json_wide.h) the range space of the call exceeds 0xFFFFFFF0 slots
+# what include/sjgpu_pretty.h declares (prettify(element) per cell, by either road); the bindings are the free functions of simdjson_amd/pretty_text.py
+PRETTY_EXPORTS = ["sjgpu_prettify_cells_device", "sjgpu_prettify_cells_wide_device"]
 
 
 # what include/sjgpu_write.h declares (typed columns as JSON records: one object per row into offsets + chars); the bindings are the free functions of
@@ -274,6 +276,10 @@ def load_library():
     L.sjgpu_serialize_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_serialize_cells_wide_device.restype = ctypes.c_int
     L.sjgpu_serialize_cells_wide_device.argtypes = L.sjgpu_serialize_cells_device.argtypes
+    L.sjgpu_prettify_cells_device.restype = ctypes.c_int
+    L.sjgpu_prettify_cells_device.argtypes = L.sjgpu_serialize_cells_device.argtypes
+    L.sjgpu_prettify_cells_wide_device.restype = ctypes.c_int
+    L.sjgpu_prettify_cells_wide_device.argtypes = L.sjgpu_serialize_cells_device.argtypes
     L.sjgpu_write_records_device.restype = ctypes.c_int
     L.sjgpu_write_records_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, vp, u64p]
     L.sjgpu_write_nested_device.restype = ctypes.c_int

@@ -1,6 +1,8 @@
 // simdjson_amd/csrc/sj_json_walk.h -- the one-lane walk of a cell's sub-tape, writing or counting its JSON text: what k_json_count / k_json_fill (sjgpu_json.hip) and the
 // kernels of sjgpu_json_wide.hip share, the code as it was measured in sjgpu_json.hip, unchanged.  Device code: include it behind sjgpu_device.h, sj_json_text.h and
 // sj_query_program.h, inside a unit's own anonymous namespace (every unit gets its own copy).
+// PRETTY = true is the reference's pretty_formatter (include/sjgpu_pretty.h): the same walk with a layout around every word, decided at compile time --
+// the minify instantiations hold none of it.
 #ifndef SJGPU_SJ_JSON_WALK_H
 #define SJGPU_SJ_JSON_WALK_H
 
@@ -44,6 +46,23 @@ struct json_sink {
     if (FILL && at < room) { out[at] = u8(c); }
     at++;
   }
+  // n blanks, n a multiple of 4 up to 60 (an indent): sixteen, eight and four at a time while they fit, wherever they begin
+  __device__ __forceinline__ void put_spaces(u32 n) {
+    if (FILL && at + n <= room) {
+      const u64 blanks[2] = {0x2020202020202020ull, 0x2020202020202020ull};
+      u8 *p = out + at;
+      u32 i = 0;
+      for (; i + 16u <= n; i += 16u) { __builtin_memcpy(p + i, blanks, 16); }
+      if (i + 8u <= n) {
+        __builtin_memcpy(p + i, blanks, 8);
+        i += 8u;
+      }
+      if (i + 4u <= n) { __builtin_memcpy(p + i, blanks, 4); }
+      at += n;
+    } else {
+      for (u32 i = 0; i < n; i++) { put(' '); }
+    }
+  }
   __device__ __forceinline__ void put_literal(u32 t) { // t, f, n
     if (t == 't') {
       put('t'); put('r'); put('u'); put('e');
@@ -83,7 +102,10 @@ struct json_sink {
 // The text of the container whose opening word is tape[low] and whose closing word is tape[high - 1] (k_rows_locate found both inside the document that begins at
 // `base`, and the opening word to say so).  -> true with the length in sink.at; false: the sub-tape is not well formed (only !FILL decides that in full -- the fill
 // runs behind a count that said true, keeps every bound and stops at the sink's room)
-template <bool FILL>
+// PRETTY: with l = (the containers open around a word) mod 16, a child of a container lies behind "\n" and 4 l blanks, a , in front of them from the second child on;
+// a value follows its key's ": "; a container that has children closes behind "\n" and its own 4 l blanks.  A container with l = 15 is FLAT -- the reference leaves its
+// loop there and starts afresh for every child --: no newline and no blank inside it, its children have l = 0 again, and each of them, like the root, ends with "\n"
+template <bool FILL, bool PRETTY = false>
 __device__ __forceinline__ bool walk_cell(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 low, u64 high, u64 base, u64 str_base, u64 str_end, u64 *strip,
                                           json_sink<FILL> &sink) {
   level_bits levels = {0, strip};
@@ -101,8 +123,13 @@ __device__ __forceinline__ bool walk_cell(const u64 *__restrict__ tape, const u8
         const u64 ow = tape[o];
         if (u32(ow >> 56) != (in_object ? u32('{') : u32('[')) || base + (ow & LOW32) != i + 1u) { return false; }
       }
-      sink.put(t);
       depth--;
+      if (PRETTY && need != 0 && (depth & 15u) != 15u) { // (need == 0: the word in front opened it)
+        sink.put('\n');
+        sink.put_spaces(4u * (depth & 15u));
+      }
+      sink.put(t);
+      if (PRETTY && (depth & 15u) == 0) { sink.put('\n'); }
       i++;
       if (depth == 0) { return i == high; }
       in_object = levels.get(depth - 1u);
@@ -115,6 +142,15 @@ __device__ __forceinline__ bool walk_cell(const u64 *__restrict__ tape, const u8
     if (is_key && t != '"') { return false; }
     if (need == 1) { sink.put(','); }
     if (need == 2) { sink.put(':'); }
+    const bool restart = PRETTY && (depth & 15u) == 0; // the root, or a child of a flat container
+    if (PRETTY && depth != 0 && !restart) {
+      if (need == 2) {
+        sink.put(' ');
+      } else {
+        sink.put('\n');
+        sink.put_spaces(4u * (depth & 15u));
+      }
+    }
     if (t == '{' || t == '[') {
       if (depth >= JSON_MAX_LEVELS) { return false; }
       in_object = t == '{';
@@ -146,6 +182,7 @@ __device__ __forceinline__ bool walk_cell(const u64 *__restrict__ tape, const u8
     } else {
       return false;
     }
+    if (PRETTY && restart && !is_key) { sink.put('\n'); }
     need = is_key ? 2u : 1u;
     key_next = in_object && !is_key;
   }
@@ -153,7 +190,8 @@ __device__ __forceinline__ bool walk_cell(const u64 *__restrict__ tape, const u8
 }
 
 // the text of root r: a scalar from the cell itself, a located container from its sub-tape.  -> its status; the length in sink.at (0 with a status)
-template <bool FILL>
+// (PRETTY: every served text ends with "\n")
+template <bool FILL, bool PRETTY = false>
 __device__ __forceinline__ u32 serialize_root(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table, u32 m, u32 t, u64 v,
                                               u64 *strip, json_sink<FILL> &sink) {
   bool ok = true;
@@ -170,11 +208,12 @@ __device__ __forceinline__ u32 serialize_root(const u64 *__restrict__ tape, cons
     } else {
       sink.put_literal(t);
     }
+    if (PRETTY && ok) { sink.put('\n'); }
   } else {
     const uint4 a = *reinterpret_cast<const uint4 *>(table + m), b = *reinterpret_cast<const uint4 *>(table + m + 1u);
     const u64 base = a.z, doc_end = b.z, str_base = a.w, str_end = b.w;
     const u64 low = v & LOW32, high = v >> 32;
-    ok = high <= doc_end && walk_cell<FILL>(tape, sbuf, low, high, base, str_base, str_end, strip, sink);
+    ok = high <= doc_end && walk_cell<FILL, PRETTY>(tape, sbuf, low, high, base, str_base, str_end, strip, sink);
   }
   if (!ok) {
     sink.at = 0;

@@ -11,6 +11,7 @@
 #include "sjgpu_dict.h"
 #include "sjgpu_json.h"
 #include "sjgpu_json_wide.h"
+#include "sjgpu_pretty.h"
 #include "sjgpu_write.h"
 #include "sj_path_program.h"
 #include "sj_write_table.h"
@@ -734,9 +735,10 @@ int sjgpu_cell_sizes_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_
 
 // ---- cells as JSON text (k_json_count, k_json_fill in sjgpu_json.hip; include/sjgpu_json.h) --------------------------------------------------------------
 // The fields call's prologue and shape: the verdicts in the context's block, the count's total read back, the fill only when it fits
-int sjgpu_serialize_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
-                                 const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev, uint64_t chars_cap,
-                                 void *stream, uint64_t *bytes_out) {
+// (pretty: sjgpu_prettify_cells_device, include/sjgpu_pretty.h -- the same call around the other instantiation of the two kernels)
+static int serialize_cells(bool pretty, sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                           const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev, uint64_t chars_cap,
+                           void *stream, uint64_t *bytes_out) {
   if (bytes_out) { *bytes_out = 0; }
   if (!string_buf_dev || !offsets_dev || !bytes_out || (rows && !status_dev) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
   if (reinterpret_cast<uintptr_t>(offsets_dev) & 3u) { return SJGPU_E_BADARG; }
@@ -756,8 +758,8 @@ int sjgpu_serialize_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t 
   const uint64_t *root_value = static_cast<const uint64_t *>(root_value_dev);
   const uint8_t *root_tag = static_cast<const uint8_t *>(root_tag_dev);
   uint32_t *where = reinterpret_cast<uint32_t *>(ctx->d_query + 256);
-  const count_total_dev *total_dev = launch_json_count(tape, sbuf, string_bytes, table, docs, root_value, root_tag, rows, where, offsets, static_cast<uint8_t *>(status_dev),
-                                                       ctx->d_tmp, s);
+  const count_total_dev *total_dev = (pretty ? launch_pretty_count : launch_json_count)(tape, sbuf, string_bytes, table, docs, root_value, root_tag, rows, where, offsets,
+                                                                                        static_cast<uint8_t *>(status_dev), ctx->d_tmp, s);
   SJ_TRY(ctx, hipGetLastError());
   uint64_t *const total = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(ctx->h_result) + 192);
   SJ_TRY(ctx, hipMemcpyAsync(total, &total_dev->total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -767,19 +769,33 @@ int sjgpu_serialize_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t 
   if (bytes > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
   if (bytes > chars_cap) { return SJGPU_E_OVERFLOW; }
   if (bytes) {
-    launch_json_fill(tape, sbuf, string_bytes, table, root_value, root_tag, rows, where, offsets, static_cast<uint8_t *>(chars_dev), ctx->d_tmp, s);
+    (pretty ? launch_pretty_fill : launch_json_fill)(tape, sbuf, string_bytes, table, root_value, root_tag, rows, where, offsets, static_cast<uint8_t *>(chars_dev), ctx->d_tmp, s);
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s)); // (the verdicts and the workspace are free again when the call returns)
   }
   return 0;
 }
 
+int sjgpu_serialize_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                                 const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev, uint64_t chars_cap,
+                                 void *stream, uint64_t *bytes_out) {
+  return serialize_cells(false, ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, root_value_dev, root_tag_dev, rows, offsets_dev, status_dev, chars_dev, chars_cap,
+                         stream, bytes_out);
+}
+int sjgpu_prettify_cells_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev, uint32_t docs,
+                                const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev, uint64_t chars_cap,
+                                void *stream, uint64_t *bytes_out) {
+  return serialize_cells(true, ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, root_value_dev, root_tag_dev, rows, offsets_dev, status_dev, chars_dev, chars_cap,
+                         stream, bytes_out);
+}
+
 // ---- cells as JSON text, breadth first (sjgpu_json_wide.hip; include/sjgpu_json_wide.h) ------------------------------------------------------------------------
 // The narrow call's refusals, prologue and decisions, word for word.  Two waits in front of the fill: the size of the range space sizes the workspace (and is what
 // SJGPU_E_RANGE refuses), the total decides the fill.  The roots' block lies behind the context's query block, the slots' in d_tmp
-int sjgpu_serialize_cells_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
-                                      uint32_t docs, const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev,
-                                      uint64_t chars_cap, void *stream, uint64_t *bytes_out) {
+// (pretty: sjgpu_prettify_cells_wide_device, include/sjgpu_pretty.h)
+static int serialize_cells_wide(bool pretty, sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                                uint32_t docs, const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev,
+                                uint64_t chars_cap, void *stream, uint64_t *bytes_out) {
   if (bytes_out) { *bytes_out = 0; }
   if (!string_buf_dev || !offsets_dev || !bytes_out || (rows && !status_dev) || (chars_cap && !chars_dev)) { return SJGPU_E_BADARG; }
   if (reinterpret_cast<uintptr_t>(offsets_dev) & 3u) { return SJGPU_E_BADARG; }
@@ -814,8 +830,8 @@ int sjgpu_serialize_cells_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint
     const size_t narrow = (json_workspace_bytes(rows) + 255) & ~size_t(255);
     rc = ensure_tmp(ctx, narrow + (size_t(rows) + 1) * sizeof(uint32_t));
     if (rc) { return rc; }
-    (void)launch_json_count(tape, sbuf, string_bytes, table, docs, root_value, root_tag, rows, json_wide_where(root_space, rows),
-                            reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->d_tmp) + narrow), status, ctx->d_tmp, s);
+    (void)(pretty ? launch_pretty_count : launch_json_count)(tape, sbuf, string_bytes, table, docs, root_value, root_tag, rows, json_wide_where(root_space, rows),
+                                                             reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(ctx->d_tmp) + narrow), status, ctx->d_tmp, s);
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s));
     return SJGPU_E_RANGE;
@@ -823,7 +839,7 @@ int sjgpu_serialize_cells_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint
   rc = ensure_tmp(ctx, json_wide_word_bytes(rows, range_words));
   if (rc) { return rc; }
   const count_total_dev *total_dev = nullptr;
-  SJ_TRY(ctx, launch_json_wide_count(tape, sbuf, string_bytes, table, root_value, root_tag, rows, range_words, offsets, status, root_space, ctx->d_tmp, s, &total_dev));
+  SJ_TRY(ctx, (pretty ? launch_pretty_wide_count : launch_json_wide_count)(tape, sbuf, string_bytes, table, root_value, root_tag, rows, range_words, offsets, status, root_space, ctx->d_tmp, s, &total_dev));
   SJ_TRY(ctx, hipGetLastError());
   SJ_TRY(ctx, hipMemcpyAsync(total, &total_dev->total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   SJ_TRY(ctx, hipStreamSynchronize(s));
@@ -832,11 +848,25 @@ int sjgpu_serialize_cells_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint
   if (bytes > 0xFFFFFFFFull) { return E_CAPACITY; } // the offsets are 32 bits
   if (bytes > chars_cap) { return SJGPU_E_OVERFLOW; }
   if (bytes) {
-    launch_json_wide_fill(tape, sbuf, string_bytes, table, root_value, root_tag, rows, range_words, static_cast<uint8_t *>(chars_dev), root_space, ctx->d_tmp, s);
+    (pretty ? launch_pretty_wide_fill : launch_json_wide_fill)(tape, sbuf, string_bytes, table, root_value, root_tag, rows, range_words, static_cast<uint8_t *>(chars_dev), root_space,
+                                                               ctx->d_tmp, s);
     SJ_TRY(ctx, hipGetLastError());
     SJ_TRY(ctx, hipStreamSynchronize(s)); // (the roots' block and the workspace are free again when the call returns)
   }
   return 0;
+}
+
+int sjgpu_serialize_cells_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                                      uint32_t docs, const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev,
+                                      uint64_t chars_cap, void *stream, uint64_t *bytes_out) {
+  return serialize_cells_wide(false, ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, root_value_dev, root_tag_dev, rows, offsets_dev, status_dev, chars_dev,
+                              chars_cap, stream, bytes_out);
+}
+int sjgpu_prettify_cells_wide_device(sjgpu_ctx *ctx, const void *tape_dev, uint64_t tape_words, const void *string_buf_dev, uint64_t string_bytes, const void *docs_dev,
+                                     uint32_t docs, const void *root_value_dev, const void *root_tag_dev, uint32_t rows, void *offsets_dev, void *status_dev, void *chars_dev,
+                                     uint64_t chars_cap, void *stream, uint64_t *bytes_out) {
+  return serialize_cells_wide(true, ctx, tape_dev, tape_words, string_buf_dev, string_bytes, docs_dev, docs, root_value_dev, root_tag_dev, rows, offsets_dev, status_dev, chars_dev,
+                              chars_cap, stream, bytes_out);
 }
 
 // ---- typed columns as JSON records (k_write_count, k_write_fill in sjgpu_write.hip; include/sjgpu_write.h) -------------------------------------------------

@@ -420,6 +420,11 @@ const count_total_dev *launch_json_count(const uint64_t *tape, const uint8_t *st
                                          const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s);
 void launch_json_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
                       uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s);
+// (launch_pretty_*: the same launches around the kernels' PRETTY instantiations, sjgpu_prettify_cells_device of include/sjgpu_pretty.h; the same workspace)
+const count_total_dev *launch_pretty_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value,
+                                           const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s);
+void launch_pretty_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                        uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s);
 // ---- cells as JSON text, breadth first (sjgpu_json_wide.hip: sjgpu_serialize_cells_wide_device, include/sjgpu_json_wide.h) -------------------------------------
 // rows >= 1, docs >= 0; a table that passed the check.  Two blocks of device memory, both 256-byte aligned: root_space, json_wide_root_bytes(rows), which holds the
 // verdicts of k_rows_locate (json_wide_where), the roots' first slots and their flags; word_space, json_wide_word_bytes(rows, R), asked for once R is known.
@@ -438,6 +443,12 @@ hipError_t launch_json_wide_count(const uint64_t *tape, const uint8_t *string_bu
                                   hipStream_t s, const count_total_dev **total);
 void launch_json_wide_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
                            uint32_t rows, uint64_t range_words, uint8_t *chars, void *root_space, void *word_space, hipStream_t s);
+// (launch_pretty_wide_*: sjgpu_prettify_cells_wide_device of include/sjgpu_pretty.h, behind the same launch_json_wide_extents and over the same two blocks)
+hipError_t launch_pretty_wide_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value,
+                                    const uint8_t *root_tag, uint32_t rows, uint64_t range_words, uint32_t *offsets, uint8_t *status, void *root_space, void *word_space,
+                                    hipStream_t s, const count_total_dev **total);
+void launch_pretty_wide_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                             uint32_t rows, uint64_t range_words, uint8_t *chars, void *root_space, void *word_space, hipStream_t s);
 // ---- typed columns as JSON records (sjgpu_write.hip: sjgpu_write_records_device, include/sjgpu_write.h) -----------------------------------------------------
 // One column as the kernels read it, K of them in device memory (sj_write_table.h makes them from the caller's sjgpu_write_column and escapes the keys):
 // key_at / key_len: the column's escaped "key": prefix inside the `keys` bytes.

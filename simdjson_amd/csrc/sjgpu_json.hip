@@ -14,6 +14,7 @@
 // beyond level 63.  The grid is capped at JSON_MAX_WORKGROUPS so that the strips stay at 512 x 256 x 504 bytes = 63 MiB at the most; a call of fewer rows takes less.
 // No per-lane array is indexed at run time: digits and escapes go straight to their place in the output (sj_dtoa.h, sj_json_text.h).
 // Every loop is bounded by the cell's high - low words, by a string's length or by a number's 20 digits; no lane waits for another.
+// PRETTY = true: sjgpu_prettify_cells_device (include/sjgpu_pretty.h), simdjson::prettify(element) -- the same two kernels with the layout of sj_json_walk.h compiled in.
 // Cost, not hidden (include/sjgpu_json.h): one lane per cell, a double is converted in both passes, bytes leave one lane at a time.
 #include "sjgpu_device.h"
 #include "sjgpu_json.h"
@@ -26,6 +27,7 @@ namespace {
 
 // grid: at most JSON_MAX_WORKGROUPS workgroups; lane = cell, grid-stride.  offsets[r] = the low 32 bits of cell r's length, offsets[rows] = 0, status[r];
 // block_sums[workgroup] = the lengths of its cells in 64 bits
+template <bool PRETTY>
 __global__ __launch_bounds__(JSON_THREADS) void k_json_count(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table,
                                                              const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where, u32 rows,
                                                              u64 *__restrict__ strips, u32 *__restrict__ offsets, u8 *__restrict__ status, u64 *__restrict__ block_sums) {
@@ -35,7 +37,7 @@ __global__ __launch_bounds__(JSON_THREADS) void k_json_count(const u64 *__restri
   u64 sum = 0;
   for (u64 r = lane_global; r < rows; r += stride) {
     json_sink<false> sink = {nullptr, 0, 0};
-    const u32 code = serialize_root<false>(tape, sbuf, string_bytes, table, where[r], root_tag[r], root_value[r], strip, sink);
+    const u32 code = serialize_root<false, PRETTY>(tape, sbuf, string_bytes, table, where[r], root_tag[r], root_value[r], strip, sink);
     offsets[r] = u32(sink.at);
     status[r] = u8(code);
     sum += sink.at;
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(JSON_THREADS) void k_json_count(const u64 *__restri
 }
 
 // the same grid.  The bytes of cell r are chars[offsets[r] .. offsets[r + 1]): only a served cell has any
+template <bool PRETTY>
 __global__ __launch_bounds__(JSON_THREADS) void k_json_fill(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table,
                                                             const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where, u32 rows,
                                                             u64 *__restrict__ strips, const u32 *__restrict__ offsets, u8 *__restrict__ chars) {
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(JSON_THREADS) void k_json_fill(const u64 *__restric
     const u64 begin = offsets[r], end = offsets[r + 1u];
     if (begin >= end) { continue; }
     json_sink<true> sink = {chars + begin, end - begin, 0};
-    (void)serialize_root<true>(tape, sbuf, string_bytes, table, where[r], root_tag[r], root_value[r], strip, sink);
+    (void)serialize_root<true, PRETTY>(tape, sbuf, string_bytes, table, where[r], root_tag[r], root_value[r], strip, sink);
   }
 }
 
@@ -89,26 +92,45 @@ static inline json_workspace carve_json_workspace(void *base, u32 rows) {
   return w;
 }
 
+template <bool PRETTY>
+static const count_total_dev *json_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value,
+                                         const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s) {
+  const json_workspace w = carve_json_workspace(workspace, rows);
+  const u32 blocks = json_blocks(rows);
+  launch_rows_locate(tape, table, docs, root_value, root_tag, rows, where, s);
+  hipLaunchKernelGGL(k_json_count<PRETTY>, dim3(blocks), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag, static_cast<const u32 *>(where), rows,
+                     w.strips, offsets, status, w.block_sums);
+  launch_count_total(w.block_sums, blocks, rows, w.ctrl, s);
+  enqueue_scan(reinterpret_cast<int *>(offsets), rows + 1u, &w.ctrl->n_plus_1, w.partial, s);
+  return w.ctrl;
+}
+template <bool PRETTY>
+static void json_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                      uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s) {
+  const json_workspace w = carve_json_workspace(workspace, rows);
+  hipLaunchKernelGGL(k_json_fill<PRETTY>, dim3(json_blocks(rows)), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag, where, rows, w.strips, offsets,
+                     chars);
+}
+
 } // namespace
 
 size_t json_workspace_bytes(uint32_t rows) { return carve_json_workspace(nullptr, rows).bytes; }
 
 const count_total_dev *launch_json_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value,
                                          const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s) {
-  const json_workspace w = carve_json_workspace(workspace, rows);
-  const u32 blocks = json_blocks(rows);
-  launch_rows_locate(tape, table, docs, root_value, root_tag, rows, where, s);
-  hipLaunchKernelGGL(k_json_count, dim3(blocks), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag, static_cast<const u32 *>(where), rows, w.strips,
-                     offsets, status, w.block_sums);
-  launch_count_total(w.block_sums, blocks, rows, w.ctrl, s);
-  enqueue_scan(reinterpret_cast<int *>(offsets), rows + 1u, &w.ctrl->n_plus_1, w.partial, s);
-  return w.ctrl;
+  return json_count<false>(tape, string_buf, string_bytes, table, docs, root_value, root_tag, rows, where, offsets, status, workspace, s);
 }
-
 void launch_json_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
                       uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s) {
-  const json_workspace w = carve_json_workspace(workspace, rows);
-  hipLaunchKernelGGL(k_json_fill, dim3(json_blocks(rows)), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag, where, rows, w.strips, offsets, chars);
+  json_fill<false>(tape, string_buf, string_bytes, table, root_value, root_tag, rows, where, offsets, chars, workspace, s);
+}
+const count_total_dev *launch_pretty_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, uint32_t docs, const uint64_t *root_value,
+                                           const uint8_t *root_tag, uint32_t rows, uint32_t *where, uint32_t *offsets, uint8_t *status, void *workspace, hipStream_t s) {
+  return json_count<true>(tape, string_buf, string_bytes, table, docs, root_value, root_tag, rows, where, offsets, status, workspace, s);
+}
+void launch_pretty_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                        uint32_t rows, const uint32_t *where, const uint32_t *offsets, uint8_t *chars, void *workspace, hipStream_t s) {
+  json_fill<true>(tape, string_buf, string_bytes, table, root_value, root_tag, rows, where, offsets, chars, workspace, s);
 }
 
 } // namespace sjgpu

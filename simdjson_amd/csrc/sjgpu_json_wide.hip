@@ -28,6 +28,9 @@
 //   k_jw_fill          one lane per head, writing at its own offset and never at or beyond the next one's; k_jw_fill_deep: the one-lane walk for the deep roots
 // The number of launches depends neither on the data nor on the nesting depth; every loop is bounded by log2(rows), by a string's length or by a number's 20 digits,
 // except the walk of a root deeper than 63 levels; nobody waits for anybody.  A string is still one lane's work, and so is a double, converted in both passes.
+// PRETTY = true: sjgpu_prettify_cells_wide_device (include/sjgpu_pretty.h).  The layout of a word is a function of what k_jw_count knows already -- the
+// depth d, the kind and the parity of its level -- and of one fact more, whether the word in front of a closing word opened it: pre[r] then holds a code, not a byte
+// (jw_layout below), and k_jw_fill writes the newline, the indent, the blank behind a key's colon and the closing newline from it.  No launch more, no byte of workspace more.
 // The staged road of k_write_fill (a workgroup's span through LDS, 16-byte stores) is NOT built: k_jw_fill writes direct stores.
 #include "sjgpu_device.h"
 #include "sjgpu_json_wide.h"
@@ -42,6 +45,13 @@ constexpr u32 JW_THREADS = 256, JW_WAVES = JW_THREADS / 64;
 constexpr u32 JW_BAD = 1u, JW_DEEP = 2u; // a root's flags
 constexpr u32 JW_LEVELS = 64;            // the levels below a root that the two vectors hold
 
+// PRETTY, what stands around a word's text, in pre[r]: bits 0-2 what lies in front, bits 3-6 the level l whose 4 l blanks follow a newline, bit 7 a newline behind
+constexpr u32 JW_NONE = 0, JW_COMMA = 1, JW_COLON = 2, JW_COLON_BLANK = 3, JW_LINE = 4, JW_COMMA_LINE = 5;
+__device__ __forceinline__ u32 jw_layout(u32 front, u32 l, bool line_behind) { return front | (l << 3) | (line_behind ? 128u : 0u); }
+__device__ __forceinline__ u32 jw_layout_bytes(u32 p) {
+  const u32 front = p & 7u, indent = 4u * ((p >> 3) & 15u);
+  return (front == JW_NONE ? 0u : front == JW_COMMA || front == JW_COLON ? 1u : front == JW_COLON_BLANK ? 2u : front == JW_LINE ? 1u + indent : 2u + indent) + (p >> 7);
+}
 __device__ __forceinline__ bool jw_is_number(u32 t) { return t == 'l' || t == 'u' || t == 'd'; }
 __device__ __forceinline__ bool jw_opens(u32 t) { return t == '{' || t == '['; }
 __device__ __forceinline__ bool jw_closes(u32 t) { return t == '}' || t == ']'; }
@@ -290,6 +300,8 @@ __device__ __forceinline__ bool jw_string_record(const u8 *__restrict__ sbuf, u6
 
 // len[r] = the low 32 bits of the length of slot r's text, pre[r] = the byte in front of it (0 , :); what is above 32 bits is added to root_high[e]; a word that the
 // walk would refuse flags its root BAD.  A slot of its own is served here as serialize_root serves it, with its status
+// PRETTY: pre[r] = jw_layout of what stands around the word's text, and the length counts it
+template <bool PRETTY>
 __global__ __launch_bounds__(JW_THREADS) void k_jw_count(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table,
                                                          const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where,
                                                          const u32 *__restrict__ start, u32 rows, u32 R, const u8 *__restrict__ head, const int *__restrict__ depth,
@@ -327,7 +339,7 @@ __global__ __launch_bounds__(JW_THREADS) void k_jw_count(const u64 *__restrict__
   bool bad = false;
   if (!s.container) {
     json_sink<false> sink = {nullptr, 0, 0};
-    status[s.e] = u8(serialize_root<false>(tape, sbuf, string_bytes, table, s.m, root_tag[s.e], root_value[s.e], nullptr, sink));
+    status[s.e] = u8(serialize_root<false, PRETTY>(tape, sbuf, string_bytes, table, s.m, root_tag[s.e], root_value[s.e], nullptr, sink));
     length = sink.at;
   } else if (!(root_flag[s.e] & JW_DEEP) && is_head) {
     const u32 t = u32(s.w >> 56);
@@ -344,6 +356,13 @@ __global__ __launch_bounds__(JW_THREADS) void k_jw_count(const u64 *__restrict__
         bad = bad || u32(ow >> 56) != (in_object ? u32('{') : u32('[')) || base + (ow & LOW32) != s.i + 1u;
       }
       length = 1;
+      if (PRETTY && d != 0) {
+        const u32 l = (d - 1u) & 15u; // the level of the container that closes here
+        const bool empty = head[r - 1u] != 0 && jw_opens(u32(tape[s.i - 1u] >> 56)); // (d != 0: a word of this root lies in front)
+        const u32 front = !empty && l != 15u ? JW_LINE : JW_NONE;
+        prefix = jw_layout(front, l, l == 0);
+        length += jw_layout_bytes(prefix);
+      }
     } else {
       bad = last || (s.j != 0 && d == 0); // the last word closes the root, and nothing else stands at its level
       if (s.j != 0) {
@@ -351,6 +370,12 @@ __global__ __launch_bounds__(JW_THREADS) void k_jw_count(const u64 *__restrict__
         bad = bad || (is_key && t != '"');
         const bool first = head[r - 1u] != 0 && jw_opens(u32(tape[s.i - 1u] >> 56));
         prefix = first ? 0u : (in_object && odd ? u32(':') : u32(','));
+        if (PRETTY) {
+          const u32 l = d & 15u;
+          const bool flat = l == 0; // (d != 0 behind a root's first slot, or the root is BAD: the parent is a container with l = 15)
+          const u32 front = in_object && odd ? (flat ? JW_COLON : JW_COLON_BLANK) : first ? (flat ? JW_NONE : JW_LINE) : (flat ? JW_COMMA : JW_COMMA_LINE);
+          prefix = jw_layout(front, l, flat && !is_key && !jw_opens(t));
+        }
       }
       if (jw_opens(t)) {
         length = 1;
@@ -372,7 +397,7 @@ __global__ __launch_bounds__(JW_THREADS) void k_jw_count(const u64 *__restrict__
       } else {
         bad = true;
       }
-      length += prefix ? 1u : 0u;
+      length += PRETTY ? jw_layout_bytes(prefix) : (prefix ? 1u : 0u);
     }
   } else if (!(root_flag[s.e] & JW_DEEP)) {
     bad = s.j + 1u == s.ext; // a number's second word where the closing word belongs
@@ -384,6 +409,7 @@ __global__ __launch_bounds__(JW_THREADS) void k_jw_count(const u64 *__restrict__
 }
 
 // one lane per located container root, grid-stride: its status; a DEEP root is walked by this lane, its length on its first slot
+template <bool PRETTY>
 __global__ __launch_bounds__(JSON_THREADS) void k_jw_roots(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table,
                                                            const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where,
                                                            const u32 *__restrict__ start, u32 rows, const u32 *__restrict__ root_flag, u32 *__restrict__ root_high,
@@ -397,7 +423,7 @@ __global__ __launch_bounds__(JSON_THREADS) void k_jw_roots(const u64 *__restrict
     u32 code = f & JW_BAD ? QUERY_NO_SUCH_FIELD : 0u;
     if (f & JW_DEEP) {
       json_sink<false> sink = {nullptr, 0, 0};
-      code = serialize_root<false>(tape, sbuf, string_bytes, table, m, root_tag[e], root_value[e], strip, sink);
+      code = serialize_root<false, PRETTY>(tape, sbuf, string_bytes, table, m, root_tag[e], root_value[e], strip, sink);
       len[start[e]] = u32(sink.at);
       root_high[e] = u32(sink.at >> 32);
     }
@@ -437,6 +463,7 @@ __global__ __launch_bounds__(JW_THREADS) void k_jw_offsets(const u32 *__restrict
 }
 
 // one lane per slot with bytes: chars[off[r] .. off[r + 1])
+template <bool PRETTY>
 __global__ __launch_bounds__(JW_THREADS) void k_jw_fill(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table,
                                                         const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where,
                                                         const u32 *__restrict__ start, u32 rows, u32 R, const u32 *__restrict__ root_flag, const u32 *__restrict__ off,
@@ -449,12 +476,23 @@ __global__ __launch_bounds__(JW_THREADS) void k_jw_fill(const u64 *__restrict__ 
   const jw_slot s = jw_slot_of(tape, root_value, where, start, rows, r);
   json_sink<true> sink = {chars + begin, end - begin, 0};
   if (!s.container) {
-    (void)serialize_root<true>(tape, sbuf, string_bytes, table, s.m, root_tag[s.e], root_value[s.e], nullptr, sink);
+    (void)serialize_root<true, PRETTY>(tape, sbuf, string_bytes, table, s.m, root_tag[s.e], root_value[s.e], nullptr, sink);
     return;
   }
   if (root_flag[s.e] & JW_DEEP) { return; } // (k_jw_fill_deep writes it)
   const u32 t = u32(s.w >> 56), prefix = pre[r];
-  if (prefix) { sink.put(prefix); }
+  if (PRETTY) {
+    const u32 front = prefix & 7u;
+    if (front == JW_COMMA || front == JW_COMMA_LINE) { sink.put(','); }
+    if (front == JW_COLON || front == JW_COLON_BLANK) { sink.put(':'); }
+    if (front == JW_COLON_BLANK) { sink.put(' '); }
+    if (front == JW_LINE || front == JW_COMMA_LINE) {
+      sink.put('\n');
+      sink.put_spaces(4u * ((prefix >> 3) & 15u));
+    }
+  } else if (prefix) {
+    sink.put(prefix);
+  }
   if (jw_opens(t) || jw_closes(t)) {
     sink.put(t);
   } else if (t == '"') {
@@ -467,8 +505,10 @@ __global__ __launch_bounds__(JW_THREADS) void k_jw_fill(const u64 *__restrict__ 
   } else {
     sink.put_literal(t);
   }
+  if (PRETTY && (prefix >> 7)) { sink.put('\n'); }
 }
 // the grid of k_jw_roots: the bytes of a DEEP root, by the walk that counted them
+template <bool PRETTY>
 __global__ __launch_bounds__(JSON_THREADS) void k_jw_fill_deep(const u64 *__restrict__ tape, const u8 *__restrict__ sbuf, u64 string_bytes, const doc_span_dev *__restrict__ table,
                                                                const u64 *__restrict__ root_value, const u8 *__restrict__ root_tag, const u32 *__restrict__ where,
                                                                const u32 *__restrict__ start, u32 rows, const u32 *__restrict__ root_flag, u64 *__restrict__ strips,
@@ -481,7 +521,7 @@ __global__ __launch_bounds__(JSON_THREADS) void k_jw_fill_deep(const u64 *__rest
     const u64 begin = off[start[e]], end = off[start[e] + 1u]; // (its other slots have no bytes)
     if (begin >= end) { continue; }
     json_sink<true> sink = {chars + begin, end - begin, 0};
-    (void)serialize_root<true>(tape, sbuf, string_bytes, table, m, root_tag[e], root_value[e], strip, sink);
+    (void)serialize_root<true, PRETTY>(tape, sbuf, string_bytes, table, m, root_tag[e], root_value[e], strip, sink);
   }
 }
 
@@ -574,9 +614,11 @@ const count_total_dev *launch_json_wide_extents(const uint64_t *tape, const doc_
   return w.ctrl;
 }
 
-hipError_t launch_json_wide_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value,
-                                  const uint8_t *root_tag, uint32_t rows, uint64_t range_words, uint32_t *offsets, uint8_t *status, void *root_space, void *word_space,
-                                  hipStream_t s, const count_total_dev **total) {
+namespace {
+template <bool PRETTY>
+hipError_t json_wide_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value,
+                           const uint8_t *root_tag, uint32_t rows, uint64_t range_words, uint32_t *offsets, uint8_t *status, void *root_space, void *word_space,
+                           hipStream_t s, const count_total_dev **total) {
   const jw_root_space A = carve_roots(root_space, rows);
   const jw_word_space W = carve_words(word_space, rows, range_words);
   const u32 R = u32(range_words), shares = jw_blocks(range_words), blocks1 = jw_blocks(range_words + 1);
@@ -594,10 +636,10 @@ hipError_t launch_json_wide_count(const uint64_t *tape, const uint8_t *string_bu
   hipLaunchKernelGGL(k_jw_maps, dim3(shares), T, 0, s, tape, root_value, static_cast<const u32 *>(A.where), static_cast<const u32 *>(A.start), rows, R,
                      static_cast<const u8 *>(W.head), static_cast<const int *>(W.depth), A.flag, W.share_map);
   hipLaunchKernelGGL(k_jw_carry_map, dim3(1), T, 0, s, W.share_map, shares);
-  hipLaunchKernelGGL(k_jw_count, dim3(shares), T, 0, s, tape, string_buf, string_bytes, table, root_value, root_tag, static_cast<const u32 *>(A.where),
+  hipLaunchKernelGGL(k_jw_count<PRETTY>, dim3(shares), T, 0, s, tape, string_buf, string_bytes, table, root_value, root_tag, static_cast<const u32 *>(A.where),
                      static_cast<const u32 *>(A.start), rows, R, static_cast<const u8 *>(W.head), static_cast<const int *>(W.depth), static_cast<const jw_map *>(W.share_map),
                      A.flag, A.high, W.len, W.pre, status);
-  hipLaunchKernelGGL(k_jw_roots, dim3(walk_blocks(rows)), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag,
+  hipLaunchKernelGGL(k_jw_roots<PRETTY>, dim3(walk_blocks(rows)), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag,
                      static_cast<const u32 *>(A.where), static_cast<const u32 *>(A.start), rows, static_cast<const u32 *>(A.flag), A.high, W.strips, W.len, status);
   hipLaunchKernelGGL(k_jw_settle, dim3(blocks1), T, 0, s, static_cast<const u32 *>(A.where), static_cast<const u32 *>(A.start), rows, R, static_cast<const u32 *>(A.flag),
                      static_cast<const u32 *>(A.high), W.len, W.block_sums);
@@ -607,16 +649,38 @@ hipError_t launch_json_wide_count(const uint64_t *tape, const uint8_t *string_bu
   return hipSuccess;
 }
 
-void launch_json_wide_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
-                           uint32_t rows, uint64_t range_words, uint8_t *chars, void *root_space, void *word_space, hipStream_t s) {
+template <bool PRETTY>
+void json_wide_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                    uint32_t rows, uint64_t range_words, uint8_t *chars, void *root_space, void *word_space, hipStream_t s) {
   const jw_root_space A = carve_roots(root_space, rows);
   const jw_word_space W = carve_words(word_space, rows, range_words);
   const u32 R = u32(range_words);
-  hipLaunchKernelGGL(k_jw_fill, dim3(jw_blocks(range_words)), dim3(JW_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag,
+  hipLaunchKernelGGL(k_jw_fill<PRETTY>, dim3(jw_blocks(range_words)), dim3(JW_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag,
                      static_cast<const u32 *>(A.where), static_cast<const u32 *>(A.start), rows, R, static_cast<const u32 *>(A.flag), static_cast<const u32 *>(W.len),
                      static_cast<const u8 *>(W.pre), chars);
-  hipLaunchKernelGGL(k_jw_fill_deep, dim3(walk_blocks(rows)), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag,
+  hipLaunchKernelGGL(k_jw_fill_deep<PRETTY>, dim3(walk_blocks(rows)), dim3(JSON_THREADS), 0, s, tape, string_buf, string_bytes, table, root_value, root_tag,
                      static_cast<const u32 *>(A.where), static_cast<const u32 *>(A.start), rows, static_cast<const u32 *>(A.flag), W.strips, static_cast<const u32 *>(W.len), chars);
+}
+
+} // namespace
+
+hipError_t launch_json_wide_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value,
+                                  const uint8_t *root_tag, uint32_t rows, uint64_t range_words, uint32_t *offsets, uint8_t *status, void *root_space, void *word_space,
+                                  hipStream_t s, const count_total_dev **total) {
+  return json_wide_count<false>(tape, string_buf, string_bytes, table, root_value, root_tag, rows, range_words, offsets, status, root_space, word_space, s, total);
+}
+void launch_json_wide_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                           uint32_t rows, uint64_t range_words, uint8_t *chars, void *root_space, void *word_space, hipStream_t s) {
+  json_wide_fill<false>(tape, string_buf, string_bytes, table, root_value, root_tag, rows, range_words, chars, root_space, word_space, s);
+}
+hipError_t launch_pretty_wide_count(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value,
+                                    const uint8_t *root_tag, uint32_t rows, uint64_t range_words, uint32_t *offsets, uint8_t *status, void *root_space, void *word_space,
+                                    hipStream_t s, const count_total_dev **total) {
+  return json_wide_count<true>(tape, string_buf, string_bytes, table, root_value, root_tag, rows, range_words, offsets, status, root_space, word_space, s, total);
+}
+void launch_pretty_wide_fill(const uint64_t *tape, const uint8_t *string_buf, uint64_t string_bytes, const doc_span_dev *table, const uint64_t *root_value, const uint8_t *root_tag,
+                             uint32_t rows, uint64_t range_words, uint8_t *chars, void *root_space, void *word_space, hipStream_t s) {
+  json_wide_fill<true>(tape, string_buf, string_bytes, table, root_value, root_tag, rows, range_words, chars, root_space, word_space, s);
 }
 
 } // namespace sjgpu
