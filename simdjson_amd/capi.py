@@ -80,6 +80,13 @@ NUMBER_OUT_OF_RANGE = 18  # what get_int64 answers a u cell, get_uint64 a negati
 SJGPU_E_OVERFLOW = -5  # (include/sjgpu.h) an output was too small; the calls with a capacity report the one they need beside it
 
 
+# what include/sjgpu_cast_strings.h declares (numbers held in strings: get_int64_in_string, get_uint64_in_string, get_double_in_string per cell)
+CAST_STRINGS_EXPORTS = ["sjgpu_cast_string_cells_device"]
+# SJGPU_GETS_*: the getter a row of sjgpu_cast_string_cells_device asks of its string cells; GETS_OR_NUMBER is a flag or-ed into it (number cells are cast as well)
+GETS_INT64, GETS_UINT64, GETS_DOUBLE, GETS_OR_NUMBER = 1, 2, 3, 0x10
+NUMBER_ERROR = 9  # what a string that is no number of the getter's kind answers where it is not INCORRECT_TYPE
+
+
 # what include/sjgpu_fields.h declares (map columns over device tapes: the fields of each cell's object, keys as string cells, and the size() of each cell's container)
 FIELDS_EXPORTS = ["sjgpu_object_fields_from_cells_device", "sjgpu_cell_sizes_device"]
 
@@ -263,6 +270,8 @@ def load_library():
     L.sjgpu_cell_kinds_device.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     L.sjgpu_cast_cells_device.restype = ctypes.c_int
     L.sjgpu_cast_cells_device.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.sjgpu_cast_string_cells_device.restype = ctypes.c_int
+    L.sjgpu_cast_string_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp, vp, vp, vp]
     L.sjgpu_object_fields_from_cells_device.restype = ctypes.c_int
     L.sjgpu_object_fields_from_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp,
                                                         ctypes.c_uint64, vp, u64p]
@@ -1052,6 +1061,58 @@ class DomParserImplementation:
 
 
 COMM_ID_BYTES = 128
+
+
+# ---- numbers held in strings (include/sjgpu_cast_strings.h): free functions over a parser, as simdjson_amd/dictionary.py's are ----------------------------------
+def cast_string_cells_device(p, strbuf_ptr, strbuf_bytes, value_ptr, tag_ptr, n, getters, value_out_ptr, code_out_ptr, valid_out_ptr, counts_out_ptr, stream=0):
+    """sjgpu_cast_string_cells_device: row k of the K = len(getters) rows of n cells asks getters[k] (GETS_INT64 / GETS_UINT64 / GETS_DOUBLE, optionally
+    | GETS_OR_NUMBER) of each of its cells, whose strings lie in strbuf_ptr[0 .. strbuf_bytes); value_out_ptr -> K * n uint64, code_out_ptr -> K * n bytes,
+    valid_out_ptr -> K * ceil(n / 64) uint64, counts_out_ptr -> K * 8 uint32; value_out_ptr / code_out_ptr may be value_ptr / tag_ptr.
+    Only enqueues.  -> 0 or a negative SJGPU_E_* for arguments the call refuses (raises on HIP errors)"""
+    g = np.array(list(getters), dtype=np.uint8)
+    rc = p.L.sjgpu_cast_string_cells_device(p.h, strbuf_ptr or None, int(strbuf_bytes), value_ptr or None, tag_ptr or None, int(n), len(g),
+                                            g.ctypes.data if len(g) else None, value_out_ptr or None, code_out_ptr or None, valid_out_ptr or None,
+                                            counts_out_ptr or None, stream or None)
+    return p._raise_infra("sjgpu_cast_string_cells_device", rc)
+
+
+def numbers_in_strings_many(p, data, row_path, pointers, getters, wide=False, max_depth=1024):
+    """table_many whose columns are numbers written inside strings (`"id_str": "505874924095815700"`): its cells stay on the device and ONE
+    sjgpu_cast_string_cells_device call asks getters[k] (GETS_INT64 / GETS_UINT64 / GETS_DOUBLE, optionally | GETS_OR_NUMBER for columns that hold numbers
+    as well) of the cells of pointer k, reading each string where it lies in the stream's string buffer.
+    -> (error_code of the first broken document or 0, documents delivered, row_offsets uint32[docs + 1], columns), columns: one dict per pointer with
+        "getter"  the getter byte                          "tags", "cells"   the column as table_many returns it, uint8[rows] / uint64[rows]
+        "values"  int64 / uint64 / float64 [rows]           "valid"   the Arrow validity buffer, uint8[ceil(rows / 64) * 8], least significant bit first
+        "codes"   uint8[rows], 0 = valid, else NUMBER_ERROR 9, INCORRECT_TYPE 17, NUMBER_OUT_OF_RANGE 18 or the code the cell held
+        "counts"  uint32[8]: valid cells, nulls, NUMBER_ERROR cells, cells that held a code, cells refused for their kind, cells decided by the exact road,
+                  string cells that point outside the buffer, 0"""
+    import torch
+    K = len(pointers)
+    if len(getters) != K:
+        raise ValueError("one getter per pointer")
+    code, docs, offsets, tags, values, strings = p._table_cells(data, row_path, pointers, max_depth, wide)
+    if offsets is None:
+        return code, docs, np.zeros(docs + 1, np.uint32), [{"getter": int(getters[k]), "tags": np.zeros(0, np.uint8), "cells": np.zeros(0, np.uint64)} for k in range(K)]
+    dev = tags.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rows = tags.shape[1]
+    W = (rows + 63) // 64
+    out_values = torch.empty((K, rows), dtype=torch.int64, device=dev)
+    out_codes = torch.empty((K, rows), dtype=torch.uint8, device=dev)
+    valid = torch.empty((K, W), dtype=torch.int64, device=dev)
+    counts = torch.zeros((K, 8), dtype=torch.int32, device=dev)
+    sbuf, sb = strings
+    _refused("sjgpu_cast_string_cells_device", cast_string_cells_device(p, sbuf.data_ptr(), sb, values.data_ptr(), tags.data_ptr(), rows, getters, out_values.data_ptr(),
+                                                                        out_codes.data_ptr(), valid.data_ptr(), counts.data_ptr(), stream))
+    torch.cuda.current_stream(dev).synchronize()
+    tags_h, cells_h = tags.cpu().numpy(), values.cpu().numpy().view(np.uint64)
+    out_h, codes_h, valid_h, counts_h = out_values.cpu().numpy(), out_codes.cpu().numpy(), valid.cpu().numpy(), counts.cpu().numpy().view(np.uint32)
+    columns = []
+    for k in range(K):
+        g = int(getters[k]) & 0x0F
+        columns.append({"getter": int(getters[k]), "tags": tags_h[k], "cells": cells_h[k], "codes": codes_h[k], "counts": counts_h[k], "valid": valid_h[k].view(np.uint8),
+                        "values": out_h[k] if g == GETS_INT64 else out_h[k].view(np.float64) if g == GETS_DOUBLE else out_h[k].view(np.uint64)})
+    return code, docs, offsets.cpu().numpy().view(np.uint32), columns
 
 
 def comm_unique_id():

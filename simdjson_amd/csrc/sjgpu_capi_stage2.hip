@@ -7,6 +7,7 @@
 #include "sjgpu_rows.h"
 #include "sjgpu_lists.h"
 #include "sjgpu_cast.h"
+#include "sjgpu_cast_strings.h"
 #include "sjgpu_fields.h"
 #include "sjgpu_dict.h"
 #include "sjgpu_json.h"
@@ -969,6 +970,22 @@ int sjgpu_cast_cells_device(sjgpu_ctx *ctx, const void *value_dev, const void *t
   SJ_TRY(ctx, hipSetDevice(ctx->device));
   SJ_TRY(ctx, launch_cast_cells(static_cast<const uint64_t *>(value_dev), static_cast<const uint8_t *>(tag_dev), n, K, getters, static_cast<uint64_t *>(value_out_dev),
                                 static_cast<uint8_t *>(code_out_dev), static_cast<uint64_t *>(valid_out_dev), static_cast<uint32_t *>(counts_out_dev), pick(ctx, stream)));
+  SJ_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+// ---- numbers held in strings (k_cast_string_cells, k_cast_strings_exact in sjgpu_cast_strings.hip; include/sjgpu_cast_strings.h) ---------------------------
+// Over the cells and the string buffer alone, as the cast above: a memset of the counters and two launches, only enqueued
+int sjgpu_cast_string_cells_device(sjgpu_ctx *ctx, const void *string_buf_dev, uint64_t string_bytes, const void *value_dev, const void *tag_dev, uint32_t n, uint32_t K,
+                                   const uint8_t *getters, void *value_out_dev, void *code_out_dev, void *valid_out_dev, void *counts_out_dev, void *stream) {
+  if (!ctx || !cast_string_cells_args_ok(string_buf_dev, string_bytes, value_dev, tag_dev, n, K, getters, value_out_dev, code_out_dev, valid_out_dev, counts_out_dev)) {
+    return SJGPU_E_BADARG;
+  }
+  if (K == 0) { return 0; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  SJ_TRY(ctx, launch_cast_string_cells(static_cast<const uint8_t *>(string_buf_dev), string_bytes, static_cast<const uint64_t *>(value_dev), static_cast<const uint8_t *>(tag_dev), n,
+                                       K, getters, static_cast<uint64_t *>(value_out_dev), static_cast<uint8_t *>(code_out_dev), static_cast<uint64_t *>(valid_out_dev),
+                                       static_cast<uint32_t *>(counts_out_dev), pick(ctx, stream)));
   SJ_TRY(ctx, hipGetLastError());
   return 0;
 }

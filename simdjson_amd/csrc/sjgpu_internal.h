@@ -382,6 +382,22 @@ inline bool cast_cells_args_ok(const void *value, const void *tag, uint32_t n, u
 hipError_t launch_cell_kinds(const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t K, uint32_t *kinds, hipStream_t s);
 hipError_t launch_cast_cells(const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t K, const uint8_t *getters, uint64_t *value_out, uint8_t *code_out,
                              uint64_t *valid_out, uint32_t *counts, hipStream_t s);
+// ---- numbers held in strings (sjgpu_cast_strings.hip: sjgpu_cast_string_cells_device, include/sjgpu_cast_strings.h) ------------------------------------------
+// What the call refuses before anything is enqueued (the C-ABI adds the null context): the cast's table with the getters 1 .. 3, optionally or-ed with 0x10, and
+// a null string buffer while it has bytes and there are cells.  The CPU tier asks the same function.
+inline bool cast_string_cells_args_ok(const void *string_buf, uint64_t string_bytes, const void *value, const void *tag, uint32_t n, uint32_t K, const uint8_t *getters,
+                                      const void *value_out, const void *code_out, const void *valid_out, const void *counts) {
+  if (K > CAST_MAX_ROWS || cast_misaligned(value, 8) || cast_misaligned(value_out, 8) || cast_misaligned(valid_out, 8) || cast_misaligned(counts, 4)) { return false; }
+  if (K && (!counts || !getters)) { return false; }
+  for (uint32_t k = 0; k < K; k++) {
+    if ((getters[k] & 0x0Fu) < 1 || (getters[k] & 0x0Fu) > 3 || (getters[k] & 0xE0u)) { return false; }
+  }
+  return !(K && n) || (value && tag && value_out && code_out && valid_out && (string_buf || !string_bytes));
+}
+// Arguments that passed the check, 1 <= K <= CAST_MAX_ROWS.  A memset of the K * 8 counters and, when n > 0, two launches: the kernel that settles what fits
+// its registers and the one that decides the cells it parked (it leaves at once where there are none).  -> what the memset returned
+hipError_t launch_cast_string_cells(const uint8_t *string_buf, uint64_t string_bytes, const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t K, const uint8_t *getters,
+                                    uint64_t *value_out, uint8_t *code_out, uint64_t *valid_out, uint32_t *counts, hipStream_t s);
 // ---- a dictionary of a row of string cells, the census per code (sjgpu_dict.hip: sjgpu_dictionary_encode_device, sjgpu_cell_kinds_by_code_device,
 // include/sjgpu_dict.h) -----------------------------------------------------------------------------------------------------------------------------------------
 // What the two calls refuse before anything is read or enqueued (the C-ABI adds the null context and *distinct_out); the CPU tier asks the same functions.
