@@ -9,7 +9,8 @@ tests/golden/json_text_golden.cpp -- a small program of our own -- is compiled a
 below.  The fixture: "documents" (a file of tests/golden/jsonexamples by name, or the bytes as hex); per case "document", "path" (hex), "cells" and either "texts"
 (hex, one per cell: a column of at most SMALL bytes) or "lengths" and "sha256" (of the texts back to back: the large columns); "doubles", one
 string of lines "<bits as 16 hex digits> <text>" (the doubles whose text is worth reading), and "double_groups": the count and the SHA-256 of the texts, joined by
-newlines, of each group of tests/json_text_cases.py's double_groups() -- the powers of two and of ten with their neighbours and the random bit patterns, made by rule.
+newlines, of each group of tests/json_text_cases.py's double_groups() -- the powers of two (the subnormal ones a group of their own) and of ten with their
+neighbours, the random bit patterns and the doubles whose top byte is a tape tag, made by rule.
 """
 import hashlib
 import json

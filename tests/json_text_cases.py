@@ -20,6 +20,7 @@ ROW_COUNTS = [0, 1, 63, 64, 65, 257]
 DEPTHS = [63, 64, 65, 70, 1100]
 MAX_DEPTH = 2048  # what the deep documents are parsed with (the parser's default, 1 024, stops short of the deepest)
 STRING_LENGTHS = list(range(18)) + [299]
+TAPE_TAGS = b'[{]}"ludtfnr'  # the top byte of every kind of tape word
 
 
 def bits_of(x):
@@ -28,7 +29,9 @@ def bits_of(x):
 
 def double_groups():
     """The bulk of the doubles' table, made by rule (the generator and the tests share it) -> {name: [bits]}: every power of two with its neighbours one ulp either
-    side (the lower one lies across the shorter interval), every power of ten with its neighbours, and seeded random bit patterns.  The fixture keeps the count and
+    side (the lower one lies across the shorter interval), every power of ten with its neighbours, seeded random bit patterns, the powers of two below the smallest
+    normal -- one mantissa bit each, down to bit pattern 1 -- with their neighbours, and 64 seeded doubles under each of the twelve tape tags as their top byte: a
+    payload word that looks like a tag word to whoever reads the tape a word at a time (all finite: no tag is 0x7F or 0xFF).  The fixture keeps the count and
     the SHA-256 of each group's texts, joined by newlines; the doubles whose text is worth reading are in its explicit table."""
     two = [b for e in range(1, 2047) for b in ((e << 52) - 1, e << 52, (e << 52) + 1)]
     ten = [bits_of(float("1e%d" % k)) + d for k in range(-323, 309) for d in (-1, 0, 1)]
@@ -37,7 +40,14 @@ def double_groups():
         b = rng.getrandbits(64)
         if (b >> 52) & 0x7FF != 0x7FF:
             rnd.append(b)
-    return {"powers_of_two": two, "powers_of_ten": ten, "random": rnd}
+    sub = []
+    for k in range(52):
+        for b in ((1 << k) - 1, 1 << k, (1 << k) + 1):
+            if b != 0 and b not in sub:
+                sub.append(b)
+    rng = random.Random(20261021)
+    tags = [(tag << 56) | rng.getrandbits(56) for tag in TAPE_TAGS for _ in range(64)]
+    return {"powers_of_two": two, "powers_of_ten": ten, "random": rnd, "subnormal_powers_of_two": sub, "tag_lookalikes": tags}
 
 
 def group_digest(texts):

@@ -33,8 +33,12 @@ def test_fixture_covers_what_it_is_for():
     assert any("\u007f/é😀 plain / text".encode() in t for t in hand)  # DEL, a solidus and the multi-byte characters leave as they are
     table = dict(doubles)
     groups, kept = json_text_cases.double_groups(), json_text_cases.fixture_double_groups()
-    assert {name: len(g) for name, g in groups.items()} == {name: d["count"] for name, d in kept.items()} == {"powers_of_two": 3 * 2046, "powers_of_ten": 3 * 632, "random": 4000}
+    assert {name: len(g) for name, g in groups.items()} == {name: d["count"] for name, d in kept.items()} == {
+        "powers_of_two": 3 * 2046, "powers_of_ten": 3 * 632, "random": 4000, "subnormal_powers_of_two": 3 * 52 - 4, "tag_lookalikes": 12 * 64}
     assert all({(e << 52) - 1, e << 52, (e << 52) + 1} <= set(groups["powers_of_two"]) for e in (1, 2, 1023, 2046))
+    sub = groups["subnormal_powers_of_two"]
+    assert sub[:5] == [1, 2, 3, 4, 5] and len(set(sub)) == len(sub) and max(sub) == (1 << 51) + 1 and all({(1 << k) - 1, 1 << k, (1 << k) + 1} <= set(sub) for k in range(1, 52))
+    assert [b >> 56 for b in groups["tag_lookalikes"]] == [t for t in json_text_cases.TAPE_TAGS for _ in range(64)] and len(set(groups["tag_lookalikes"])) == 12 * 64
     assert table[0x3FF0000000000000] == b"1.0" and table[1] == b"5e-324" and table[1 << 63] == b"-0.0" and table[0x7FEFFFFFFFFFFFFF] == b"1.7976931348623157e+308"
     assert {len(t.replace(b".", b"").replace(b"-", b"").split(b"e")[0].lstrip(b"0")) for t in table.values()} >= {1, 15, 16, 17}
 
