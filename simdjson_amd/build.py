@@ -52,7 +52,7 @@ def build_corpus(force=False):
     return _paths.LIB_CORPUS
 
 
-SJGPU_SOURCES = ("sjgpu_kernels.hip", "sjgpu_fused.hip", "sjgpu_small.hip", "sjgpu_finish.hip", "sjgpu_strings.hip", "sjgpu_string_stream.hip", "sjgpu_tape.hip", "sjgpu_tape_many.hip", "sjgpu_query.hip", "sjgpu_cast.hip", "sjgpu_cast_strings.hip", "sjgpu_dict.hip", "sjgpu_json.hip", "sjgpu_json_wide.hip", "sjgpu_write.hip",
+SJGPU_SOURCES = ("sjgpu_kernels.hip", "sjgpu_fused.hip", "sjgpu_small.hip", "sjgpu_finish.hip", "sjgpu_strings.hip", "sjgpu_string_stream.hip", "sjgpu_tape.hip", "sjgpu_tape_many.hip", "sjgpu_query.hip", "sjgpu_cast.hip", "sjgpu_cast_strings.hip", "sjgpu_dict.hip", "sjgpu_pivot.hip", "sjgpu_json.hip", "sjgpu_json_wide.hip", "sjgpu_write.hip",
                  "sjgpu_mgpu.hip", "sjgpu_comm.hip", "sjgpu_capi.hip", "sjgpu_capi_host.hip", "sjgpu_capi_stage2.hip", "stage1_finish.cpp")
 SJGPU_HEADERS = ("sj_block.h", "sj_number.h", "sj_number_in_string.h", "sj_tape_rules.h", "sj_string_stream.h", "sj_xcarry.h", "sj_pow5_table.inc", "sj_dtoa.h", "sj_pow10_table.inc", "sj_json_text.h", "sj_json_walk.h", "sj_write_table.h", "sj_nested_table.h", "sj_query_program.h", "sj_path_program.h", "sj_cell_kinds.h", "sjgpu_internal.h", "sjgpu_device.h", "sjgpu_ctx.h")
 
@@ -63,7 +63,7 @@ def sjgpu_source_stamp():
     h = hashlib.sha256()
     for f in [*_csrc(*SJGPU_SOURCES), *_csrc(*SJGPU_HEADERS), os.path.join(_paths.INCLUDE_DIR, "sjgpu.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_stream.h"),
               os.path.join(_paths.INCLUDE_DIR, "sjgpu_query.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_paths.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_rows.h"),
-              os.path.join(_paths.INCLUDE_DIR, "sjgpu_lists.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_cast.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_cast_strings.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_fields.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_dict.h"),
+              os.path.join(_paths.INCLUDE_DIR, "sjgpu_lists.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_cast.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_cast_strings.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_fields.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_dict.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_pivot.h"),
               os.path.join(_paths.INCLUDE_DIR, "sjgpu_json.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_json_wide.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_pretty.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_write.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_nested.h"), os.path.join(_paths.INCLUDE_DIR, "sjgpu_debug.h")]:
         h.update(os.path.relpath(f, _paths.REPO_ROOT).encode())
         h.update(open(f, "rb").read())

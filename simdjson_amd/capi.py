@@ -97,6 +97,11 @@ DICT_EXPORTS = ["sjgpu_dictionary_encode_device", "sjgpu_cell_kinds_by_code_devi
 SJGPU_E_INTERNAL = -7  # (include/sjgpu_dict.h) a bounded loop of the library ran out: a bug of the library
 
 
+# what include/sjgpu_pivot.h declares (a map column pivoted into a record table: one column per key code, the first field of a row that maps to a column wins); the
+# bindings are the free functions of simdjson_amd/pivot.py
+PIVOT_EXPORTS = ["sjgpu_pivot_fields_device"]
+
+
 # what include/sjgpu_json.h declares (cells as JSON text: minify(element) per cell into offsets + chars); the bindings are the free functions of
 # simdjson_amd/json_text.py
 JSON_EXPORTS = ["sjgpu_serialize_cells_device"]
@@ -281,6 +286,8 @@ def load_library():
     L.sjgpu_dictionary_encode_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_cell_kinds_by_code_device.restype = ctypes.c_int
     L.sjgpu_cell_kinds_by_code_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    L.sjgpu_pivot_fields_device.restype = ctypes.c_int
+    L.sjgpu_pivot_fields_device.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     L.sjgpu_serialize_cells_device.restype = ctypes.c_int
     L.sjgpu_serialize_cells_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64, vp, u64p]
     L.sjgpu_serialize_cells_wide_device.restype = ctypes.c_int

@@ -10,6 +10,7 @@
 #include "sjgpu_cast_strings.h"
 #include "sjgpu_fields.h"
 #include "sjgpu_dict.h"
+#include "sjgpu_pivot.h"
 #include "sjgpu_json.h"
 #include "sjgpu_json_wide.h"
 #include "sjgpu_pretty.h"
@@ -1035,6 +1036,22 @@ int sjgpu_cell_kinds_by_code_device(sjgpu_ctx *ctx, const void *codes_dev, const
   SJ_TRY(ctx, hipSetDevice(ctx->device));
   SJ_TRY(ctx, launch_cell_kinds_by_code(static_cast<const int32_t *>(codes_dev), static_cast<const uint64_t *>(value_dev), static_cast<const uint8_t *>(tag_dev), n, groups,
                                         static_cast<uint32_t *>(kinds_dev), pick(ctx, stream)));
+  SJ_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+// ---- a map column pivoted into a record table (sjgpu_pivot.hip; include/sjgpu_pivot.h) --------------------------------------------------------------------------
+// Over the fields' rows, their codes and the map alone: two launches, only enqueued -- no block of the context, no workspace, no event
+int sjgpu_pivot_fields_device(sjgpu_ctx *ctx, const void *offsets_dev, const void *status_dev, uint32_t rows, const void *codes_dev, const void *value_dev, const void *tag_dev,
+                              uint64_t fields, const void *column_of_code_dev, uint32_t groups, uint32_t columns, void *value_out_dev, void *tag_out_dev, void *stream) {
+  if (!ctx || !pivot_args_ok(offsets_dev, status_dev, rows, codes_dev, value_dev, tag_dev, fields, column_of_code_dev, groups, columns, value_out_dev, tag_out_dev)) {
+    return SJGPU_E_BADARG;
+  }
+  if (rows == 0 || columns == 0) { return 0; }
+  SJ_TRY(ctx, hipSetDevice(ctx->device));
+  launch_pivot_fields(static_cast<const uint32_t *>(offsets_dev), static_cast<const uint8_t *>(status_dev), rows, static_cast<const int32_t *>(codes_dev),
+                      static_cast<const uint64_t *>(value_dev), static_cast<const uint8_t *>(tag_dev), uint32_t(fields), static_cast<const int32_t *>(column_of_code_dev), groups,
+                      columns, static_cast<uint64_t *>(value_out_dev), static_cast<uint8_t *>(tag_out_dev), pick(ctx, stream));
   SJ_TRY(ctx, hipGetLastError());
   return 0;
 }

@@ -427,6 +427,21 @@ hipError_t launch_dict_encode(const uint64_t *value, const uint8_t *tag, uint32_
 void launch_dict_fill(const uint64_t *value, uint32_t n, void *workspace, uint64_t *dict_value, uint8_t *dict_tag, uint32_t *dict_first, uint32_t *dict_count, hipStream_t s);
 // a memset of the groups * 16 counters and, when n > 0, one launch: up to 512 groups the histogram lies in LDS, above that every cell adds to global memory
 hipError_t launch_cell_kinds_by_code(const int32_t *codes, const uint64_t *value, const uint8_t *tag, uint32_t n, uint32_t groups, uint32_t *kinds, hipStream_t s);
+// ---- a map column pivoted into a record table (sjgpu_pivot.hip: sjgpu_pivot_fields_device, include/sjgpu_pivot.h) ------------------------------------------------
+// What the call refuses before anything is enqueued (the C-ABI adds the null context); the CPU tier asks the same function.
+constexpr uint64_t PIVOT_MAX_CELLS = 0xFFFFFFF0ull;
+inline bool pivot_args_ok(const void *offsets, const void *status, uint32_t rows, const void *codes, const void *value, const void *tag, uint64_t fields,
+                          const void *column_of_code, uint32_t groups, uint32_t columns, const void *value_out, const void *tag_out) {
+  if (uint64_t(columns) * rows > PIVOT_MAX_CELLS || fields > 0xFFFFFFFFull) { return false; }
+  if (cast_misaligned(value, 8) || cast_misaligned(value_out, 8) || cast_misaligned(offsets, 4) || cast_misaligned(codes, 4) || cast_misaligned(column_of_code, 4)) { return false; }
+  if (uint64_t(columns) * rows > 0 && (!offsets || !status || !value_out || !tag_out)) { return false; }
+  if (fields > 0 && (!codes || !value || !tag)) { return false; }
+  return !(column_of_code && groups == 0);
+}
+// Arguments that passed the check, rows >= 1, columns >= 1: the fill (every cell's default) and, behind it, the scatter (one lane per row, its slots from the last
+// to the first).  Two launches, nothing else.
+void launch_pivot_fields(const uint32_t *offsets, const uint8_t *status, uint32_t rows, const int32_t *codes, const uint64_t *value, const uint8_t *tag, uint32_t fields,
+                         const int32_t *column_of_code, uint32_t groups, uint32_t columns, uint64_t *value_out, uint8_t *tag_out, hipStream_t s);
 // ---- cells as JSON text (sjgpu_json.hip: sjgpu_serialize_cells_device, include/sjgpu_json.h) -----------------------------------------------------------------
 // rows >= 1, docs >= 0, rows + 1 entries the scan takes; a table that passed the check; where[0 .. rows) (device memory): k_rows_locate's verdicts, made here;
 // workspace: json_workspace_bytes(rows), 256-byte aligned, the same for both launches.  launch_json_count: status[r] and, in offsets[0 .. rows], the exclusive sum of the
